@@ -4,6 +4,8 @@ on synthetic Snopes-shaped batches (BASELINE.json configs[1]: B=32 claims x 30 e
 D=H=300, 5 word heads / 2 evidence heads, window 3, gsl_rate 0.6, fp32).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full              # + every side measurement (see below)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR  # + the last timed step's results as DIR/*.npy
     python bench.py --gpus N ...          # RANK unset: re-executes itself under torch.distributed.run, one rank per GPU
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -12,6 +14,13 @@ One "step" = graph build from token ids + full model forward + cross-entropy + b
 gradient all-reduce (N>1) + fused Adam, with the batch already resident in HBM.  Rank 0 prints ONE
 JSON line.  Weak scaling: every rank runs its own B=32 batch (claims are independent; the only
 exchange is the gradient all-reduce).
+
+A plain run sets up, runs --warmup W steps, times exactly --steps K steps as one block, optionally
+writes the outputs of the last timed step (--dump-outputs) and prints the line.  --full adds what the
+headline figure does not need: the repeated-block statistics with the live roofline of the dominant
+kernel, the per-kernel table, the phase split, the strong-scaling leg, the side regimes, the realistic
+series, the other BASELINE configs, the parity slice against the CPU oracle, the CPU baseline and the
+box's copy / BLAS ceilings (each still switched off by its --no-* option).
 """
 import argparse
 import json
@@ -433,10 +442,13 @@ def make_step(args, wl, trainer, source="resident"):
         if args.forward_only:
             with torch.no_grad():
                 query, document, kargs = b.inputs()
-                return model(query, document, **kargs).sum()
+                phi = model(query, document, **kargs)
+                state["phi"] = phi
+                return phi.sum()
         trainer.zero_grad()
         query, document, kargs = b.inputs()
         phi = model(query, document, **kargs)
+        state["phi"] = phi                             # (a reference, no device work: what --dump-outputs writes)
         loss = ops.cross_entropy(phi, b.labels)        # losses.py:29-32, loss + gradient in one launch
         if source in ("reference", "reference_sync", "reference_host"):
             loss.backward()                            # what the unchanged fitter calls
@@ -453,6 +465,7 @@ def make_step(args, wl, trainer, source="resident"):
         p, state["pairs"] = state["pairs"], 0
         return p
 
+    step.state = state
     return step, pairs
 
 
@@ -528,6 +541,65 @@ def measure(args, wl, trainer, world, device, dist, steps, warmup, profile=True,
             "prof_dom": prof_dom, "step": step}
 
 
+def time_steps(args, wl, trainer, world, device, dist, steps, warmup):
+    """The headline protocol: `warmup` steps, then ONE block of exactly `steps` timed steps, bracketed by barrier +
+    synchronize on both sides and reduced with MAX over the ranks.  Returns the seconds of the block, the pairs this rank
+    processed in it, the last loss and the step fn (step.state["phi"]: the logits of the last step)."""
+    step, pairs_fn = make_step(args, wl, trainer)
+
+    def barrier():
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+
+    for _ in range(warmup):
+        step()
+    barrier()
+    pairs_fn()
+    loss = None
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        loss = step()
+    barrier()
+    dt = time.perf_counter() - t0
+    if world > 1:
+        t = torch.tensor([dt], device=device, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+    return {"seconds": dt, "pairs": pairs_fn(), "loss": loss, "step": step}
+
+
+DUMP_MAX_ELEMENTS = 2 << 20       # per array: larger outputs are written as a fixed, seeded sample of this many elements
+
+
+def dump_outputs(path, step, trainer, loss, forward_only):
+    """--dump-outputs: what the timed path handed its caller in the LAST timed step, as float32 / float64 .npy files --
+    logits.npy (the model's output), and for a training step loss.npy, params.npy (the parameters after the Adam update:
+    the trainer's flat fp32 buffer) and grads.npy (the flat gradient the update consumed).  An array above
+    DUMP_MAX_ELEMENTS is replaced by a seeded sample of that many elements (NAME.npy) and its flat indices
+    (NAME_index.npy); with the same arguments the inputs, and so the sample, are the same in every run."""
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {"logits": step.state["phi"]}
+    if not forward_only:
+        arrays.update(loss=loss, params=trainer.flat_p, grads=trainer.flat_g)
+    written = {}
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        a = t.detach().float().reshape(-1).cpu().numpy()
+        shape = tuple(t.shape)
+        if a.size > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(SEED).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))
+            np.save(os.path.join(path, f"{name}_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        else:
+            a = a.reshape(shape)
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
 def phase_split(wl, trainer, steps=5):
     """fwd / bwd / all-reduce / optimiser milliseconds per step: HIP events on the compute stream between the phases of
     `steps` extra, untimed steps (the events serialise the overlapped early all-reduce, so this is a breakdown, not the
@@ -594,7 +666,7 @@ BF16_BENCH_LOGIT_BOUND = 5e-3
 STRONG_GLOBAL_BATCH = 256         # BASELINE configs[3]
 
 # The BASELINE configs the headline invocation does not run as its main workload, printed beside it (`other_configs`) so that
-# the driver's `python bench.py --gpus 1` line carries a timing of each: (name, SynthConfig overrides, gemm mode, steps per block)
+# the `python bench.py --gpus 1 --full` line carries a timing of each: (name, SynthConfig overrides, gemm mode, steps per block)
 OTHER_CONFIGS = [
     ("configs[2] PolitiFact-shaped: B=64 x 10 evidences, L_right=200, fp32",
      dict(batch=64, n_evd=10, len_right=200), "fp32", 10),
@@ -772,18 +844,25 @@ def main():
                          "through batch.kargs_from_reference_tensors, packed on the device (printed beside the headline)")
     ap.add_argument("--streamed", action="store_true",
                     help="ALSO time a fresh NativeBatch per step (H2D of the ids + m_real read-back, one batch ahead on a side stream)")
-    ap.add_argument("--no-side-modes", action="store_true", help="skip the --reference-api / --streamed legs the headline run adds by default")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (off by default): the repeated-block statistics with the "
+                         "live roofline, the per-kernel table, the phase split, the strong-scaling leg, the side regimes, the "
+                         "realistic series, the other BASELINE configs, the parity slice, the CPU baseline and the box ceilings")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (logits, loss, updated parameters, "
+                         "gradients) as DIR/<name>.npy")
+    ap.add_argument("--no-side-modes", action="store_true", help="skip the --reference-api / --streamed legs the --full headline run adds by default")
     ap.add_argument("--collective", choices=["torch", "library"], default="torch",
                     help="who carries the gradient all-reduce: torch.distributed (default; backend nccl = RCCL) or the library's own "
                          "RCCL communicator (gh_comm_init / gh_flat_allreduce, include/get_hip.h); with --gpus 1 the library route "
                          "runs a world-size-1 communicator so that the collective is issued and timed on the device")
     ap.add_argument("--no-strong", dest="strong_too", action="store_false",
-                    help="skip the strong-scaling leg (configs[3]: global batch 256 split over the ranks) printed beside the weak line")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="skip the per-kernel HIP-event timing")
-    ap.add_argument("--no-series", action="store_true", help="skip the realistic evidence-count series")
+                    help="skip the strong-scaling leg (configs[3]: global batch 256 split over the ranks) a --full run prints beside the weak line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline of a --full run")
+    ap.add_argument("--no-profile", action="store_true", help="skip the per-kernel HIP-event timing of a --full run")
+    ap.add_argument("--no-series", action="store_true", help="skip the realistic evidence-count series of a --full run")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the legs of BASELINE configs[2] / configs[4] fp32 / configs[4] bf16 the headline run prints beside its line")
+                    help="skip the legs of BASELINE configs[2] / configs[4] fp32 / configs[4] bf16 the --full headline run prints beside its line")
     ap.add_argument("--cpu-threads", type=int, default=0, help="torch threads of the CPU baseline (default: the probe's fastest pool size)")
     ap.add_argument("--measure-build", action="store_true",
                     help="kernel A/B tooling only: load lib/libget_hip_measure.so (make -C get_amd/csrc measure), honour the GH_* "
@@ -876,12 +955,21 @@ def main():
         trainer.attach_overlap()             # 76 % of the gradient all-reduce runs underneath the first cell's backward
     model.train(not (args.eval_mode or args.forward_only))
 
-    m = measure(args, wl, trainer, world, device, dist, args.steps, args.warmup, profile=not args.no_profile)
-    loss, prof_dom, step = m["loss"], m["prof_dom"], m["step"]
-    comm_bytes_step = trainer.comm_bytes / max(1, (args.warmup + args.steps * len(m["blocks_s"])))
-    prof = None
+    h = time_steps(args, wl, trainer, world, device, dist, args.steps, args.warmup)
+    loss, step = h["loss"], h["step"]
+    comm_bytes_step = trainer.comm_bytes / max(1, args.warmup + args.steps)
+    comm_calls_step = trainer.comm_calls / max(1, args.warmup + args.steps)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, step, trainer, loss, args.forward_only)
+    # --full: the round-1..6 protocol of the headline as a leg of its own (untimed settle blocks, >= MIN_TIMED_BLOCKS timed
+    # blocks of K steps, median) with the live roofline of the dominant kernel in its first timed steps
+    m, prof_dom, prof = None, None, None
+    if args.full:
+        m = measure(args, wl, trainer, world, device, dist, args.steps, 0, profile=not args.no_profile)
+        prof_dom = m["prof_dom"]
     PROFILE_EXTRA_STEPS = 5
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         _lib.profile_enable(True)                       # every instrumented kernel, outside the timed region
         _lib.profile_collect()
         for _ in range(PROFILE_EXTRA_STEPS):
@@ -889,12 +977,14 @@ def main():
         torch.cuda.synchronize()
         prof = _lib.profile_collect()
         _lib.profile_enable(False)
-    split = None if args.forward_only else phase_split(wl, trainer)      # collective inside: every rank runs it
+    split = None if (args.forward_only or not args.full) else phase_split(wl, trainer)      # collective inside: every rank runs it
     # whole-job pairs per block: sum over the ranks (the per-block seconds are already MAX over ranks)
-    bp = torch.tensor(m["block_pairs"] + [float(cfg.batch * args.steps)], device=device, dtype=torch.float64)
+    bp = torch.tensor([float(h["pairs"])] + (m["block_pairs"] if m else []) + [float(cfg.batch * args.steps)], device=device,
+                      dtype=torch.float64)
     if world > 1:
         dist.all_reduce(bp, op=dist.ReduceOp.SUM)
-    world_pairs = [float(x) for x in bp[:-1].tolist()]
+    world_pairs = float(bp[0].item())
+    world_pairs_blocks = [float(x) for x in bp[1:-1].tolist()]
     total_claims_block = float(bp[-1].item())
 
     # configs[3] in the same launch: ONE global batch of STRONG_GLOBAL_BATCH claims dealt over the ranks by sort-then-stripe
@@ -904,7 +994,7 @@ def main():
     # (configs[3] is defined on the Snopes shape: only the headline shape carries the leg -- at h = 768 a 256-claim batch on one
     #  GPU is 2.4 GB per activation, past what the fast kernels' buffer descriptors address)
     strong_shape = (args.len_right, args.hidden, args.word_heads, args.window, args.n_evd) == (100, 300, 5, 3, 30)
-    if (args.strong_too and not args.no_side_modes and args.global_batch <= 0 and not args.forward_only and args.gemm_mode == "fp32" and
+    if (args.full and args.strong_too and not args.no_side_modes and args.global_batch <= 0 and not args.forward_only and args.gemm_mode == "fp32" and
             STRONG_GLOBAL_BATCH % world == 0 and strong_shape):
         gshard = (lambda counts: shard_claims(STRONG_GLOBAL_BATCH, rank, world, counts))
         cfg_s = SynthConfig(**{**cfg_in.__dict__, "batch": STRONG_GLOBAL_BATCH})
@@ -935,8 +1025,10 @@ def main():
                    (100, 300, 5, 3, 0.6, 30, "fixed") and per_rank == 32 and args.gemm_mode == "fp32" and not args.padded \
                    and not args.eval_mode and not args.forward_only
     if rank == 0:
-        summ = summarize_blocks(m, args.steps, world_pairs)
-        value, ms_per_step = summ["value"], summ["ms_per_step"]
+        value, ms_per_step = world_pairs / h["seconds"], 1e3 * h["seconds"] / args.steps
+        timed = {"blocks": 1, "steps": args.steps, "warmup_steps": args.warmup, "seconds_total": h["seconds"],
+                 "note": f"{args.warmup} warm-up steps, then ONE block of exactly {args.steps} timed steps (barrier + synchronize "
+                         "on both sides, MAX over ranks); value = whole-job pairs of the block / its seconds"}
         headline = headline_run
         real_nodes = wl["m_real"] / max(wl["b1"], 1)
         fl = flops_per_pair(cfg, wl["nnz_per_graph"], real_nodes if wl["compact"] else None)
@@ -951,12 +1043,12 @@ def main():
             "dtype": {"fp32": "f32", "bf16": "bf16 operands / f32 accumulate in the big GEMMs, f32 elsewhere"}.get(
                 args.gemm_mode, "f32 storage and results; big NT GEMM products from 3-way bf16 splits on the bf16 MFMA (opt-in)"),
             "data": "synthetic",
-            "claims_per_s": total_claims_block * value / max(float(np.median(world_pairs)), 1.0),
-            "timed": summ["timed"],
+            "claims_per_s": total_claims_block * value / max(world_pairs, 1.0),
+            "timed": timed,
             "rccl_ranks": (lib_comm.info()[1] if lib_comm is not None else (dist.get_world_size() if world > 1 else 1)),
             "collective": {"backend": backend, "allreduce_bytes_per_step_per_rank": comm_bytes_step,
                            "allreduce_ms_per_step": (split or {}).get("allreduce_ms"),
-                           "calls_per_step": trainer.comm_calls / max(1, (args.warmup + args.steps * len(m["blocks_s"]))),
+                           "calls_per_step": comm_calls_step,
                            "note": "one flat fp32 gradient bucket; the early-final range (head, attentions, second cell) is "
                                    "reduced asynchronously underneath the first cell's backward, the rest after backward"},
             "config": {"workload": ("BASELINE configs[1]: Snopes-shaped synthetic batch, " if headline
@@ -984,6 +1076,13 @@ def main():
                             "achieved_tflops_per_gpu": fl_run * value / world / 1e12,
                             "frac_of_f32_mfma_peak": fl_run * value / world / 1e12 / PEAK_F32_MFMA_TFLOPS},
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+        if m is not None:
+            summ = summarize_blocks(m, args.steps, world_pairs_blocks)
+            out["timed_blocks"] = {"pairs_per_s": summ["value"], "ms_per_step": summ["ms_per_step"], **summ["timed"],
+                                   "what": "the same step and workload, measured again after the headline block with the "
+                                           "repeated-block protocol (untimed settle blocks, then timed blocks, median)"}
         if prof is not None:
             kernels = {}
             for name, r in prof.items():
@@ -1028,7 +1127,8 @@ def main():
                                "traffic_source": traffic_src,
                                "avg_launch_ms": d["avg_launch_ms"], "launches_per_step": d["launches_per_step"],
                                "alg_flops_per_launch": prof_dom["work"] / prof_dom["launches"],
-                               "measured": f"HIP events around every {dom} launch of the first {prof_dom['steps']} timed steps"}
+                               "measured": f"HIP events around every {dom} launch of the first {prof_dom['steps']} timed steps "
+                                           "of the timed_blocks leg"}
             if dom_note:
                 out["roofline"]["note"] = dom_note
             out["kernels_note"] = (f"per-kernel table from {PROFILE_EXTRA_STEPS} extra untimed steps with every library "
@@ -1038,9 +1138,9 @@ def main():
             out["step_split_ms"] = split
         if strong is not None:
             out["strong_scaling"] = strong
-        if not args.no_profile and world == 1:
+        if args.full and not args.no_profile and world == 1:
             out["box_reference"] = box_reference(device)
-    default_side = (world == 1 and headline_run and not args.no_side_modes and not args.no_series)
+    default_side = (args.full and world == 1 and headline_run and not args.no_side_modes and not args.no_series)
     do_ref = world == 1 and not args.forward_only and (args.reference_api or default_side)
     do_stream = world == 1 and not args.forward_only and (args.streamed or default_side)
     if (do_ref or do_stream) and rank == 0:
@@ -1112,7 +1212,7 @@ def main():
                 _lib.set_gemm_mode("fp32")
         out["other_regimes"] = extra
     if rank == 0:
-        if world == 1 and not args.no_series and not args.forward_only and args.evd_dist == "fixed" and headline:
+        if args.full and world == 1 and not args.no_series and not args.forward_only and args.evd_dist == "fixed" and headline:
             # SURVEY 8(d) "realistic series": evidence counts from the empirical Snopes histogram (mean 6.9 per claim);
             # at B = 32 that is ~220 pairs per step, at B = 139 about the headline's 960
             series = []
@@ -1135,9 +1235,9 @@ def main():
             # the other BASELINE configs as legs of the same run (two of five configs had no driver-observed timing)
             out["other_configs"] = [other_config_leg(args, nm, ov, md, st, device, dist, other_config_seed(i))
                                     for i, (nm, ov, md, st) in enumerate(OTHER_CONFIGS)]
-        if world == 1 and not args.forward_only:
+        if args.full and world == 1 and not args.forward_only:
             out["parity"] = parity_check(wl)
-        if world == 1 and not args.no_cpu_baseline and not args.forward_only:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.forward_only:
             probe = cpu_baseline_probe(wl)
             cb = cpu_baseline(wl, threads=args.cpu_threads or probe["cores"])
             cb["speedup_gpu_over_cpu"] = value / cb["value"]

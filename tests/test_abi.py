@@ -8,6 +8,7 @@ import re
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -80,13 +81,20 @@ def test_state_dict_contract_matches_reference(golden_dir):
     assert not model.embedding.weight.requires_grad and model.article_source_embs.weight.requires_grad
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/MasterFC"), reason="reference tree only exists in the build container")
-def test_install_shim_resolves_reference_import_paths():
+def _reference_package_dirs(root):
+    """Empty parent packages with the reference's import paths (Models/, Models/BiDAF/, Models/FCWithEvidences/,
+    thirdparty/): the shim registers the leaf modules, a caller's tree supplies the packages above them."""
+    for pkg in ("Models", "Models/BiDAF", "Models/FCWithEvidences", "thirdparty"):
+        os.makedirs(os.path.join(root, pkg), exist_ok=True)
+        open(os.path.join(root, pkg, "__init__.py"), "w").close()
+
+
+def test_install_shim_resolves_reference_import_paths(tmp_path, golden_dir):
+    _reference_package_dirs(str(tmp_path))
     code = r"""
 import sys
 sys.path.insert(0, %r)
-from oracle import _refshim
-_refshim.install()
+sys.path.insert(0, %r)
 import get_amd
 M = get_amd.install()
 from Models.FCWithEvidences import graph_based_semantic_structure      # as MasterFC/master_get.py:5 does
@@ -94,47 +102,44 @@ from Models.BiDAF.wrapper import GGNN, GGNN_with_GSL, Linear
 from thirdparty.two_branches_attention import *
 assert graph_based_semantic_structure.Graph_basedSemantiStructure is M.Graph_basedSemantiStructure
 assert GGNN is M.GGNN and ConcatNotEqualSelfAtt is M.ConcatNotEqualSelfAtt
-import setting_keywords                                                  # the reference's own vocabulary
-from get_amd.keywords import KeyWordSettings as K
-for name in [n for n in dir(K) if not n.startswith('_') and isinstance(getattr(K, n), str)]:
-    assert getattr(setting_keywords.KeyWordSettings, name) == getattr(K, name), name
+assert graph_based_semantic_structure.KeyWordSettings is get_amd.KeyWordSettings
 print('ok')
-""" % ROOT
+""" % (ROOT, str(tmp_path))
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stderr[-2000:]
+    # the vocabulary: every key the reference fitter handed to net(...) in the captured G9 batch that the model reads is
+    # a string of the drop-in's KeyWordSettings
+    from get_amd.keywords import KeyWordSettings as K
+    z = np.load(os.path.join(golden_dir, "g9_fitter_kargs_small.npz"))
+    keys = set(json.loads(bytes(z["meta"]).decode())["keys"])
+    vocab = {v for n, v in vars(K).items() if isinstance(v, str) and not n.startswith("_")}
+    unread = {"query_content_without_padding_evidences", "query_char_source", "doc_char_source", "fc_labels"}
+    assert keys - unread <= vocab, keys - unread - vocab
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/MasterFC"), reason="reference tree only exists in the build container")
-def test_master_get_itself_imports_against_the_shim_and_builds_the_hip_backed_model():
-    """the reference's driver, MasterFC/master_get.py, imported UNMODIFIED (its own `from Models...
-    import graph_based_semantic_structure` at :5, the fitter, matchzoo, handlers) after get_amd.install(): the model class
-    it would construct at :145 is the HIP-backed drop-in, and constructing it with the params dict of :118-144 works."""
+def test_master_get_params_dict_builds_the_hip_backed_model(tmp_path):
+    """The model import of the reference's driver (MasterFC/master_get.py:5) after get_amd.install(), and the params dict its
+    fit_models builds at :118-144 (sizes shrunk): the class it constructs at :145 is the HIP-backed drop-in."""
+    _reference_package_dirs(str(tmp_path))
     code = r"""
-import sys, os
+import sys
 sys.path.insert(0, %r)
-from oracle import _refshim
-_refshim.install()
+sys.path.insert(0, %r)
 import get_amd
 M = get_amd.install()
-sys.path.insert(0, '/root/reference/MasterFC')
-os.chdir('/root/reference/MasterFC')
-import master_get                                                        # the driver module itself, top to bottom
-assert master_get.graph_based_semantic_structure.Graph_basedSemantiStructure is M.Graph_basedSemantiStructure
+from Models.FCWithEvidences import graph_based_semantic_structure
+assert graph_based_semantic_structure.Graph_basedSemantiStructure is M.Graph_basedSemantiStructure
 import numpy as np
-# the params dict master_get.fit_models builds at :118-144 (sizes shrunk)
 params = dict(embedding=np.random.rand(50, 16).astype('float32'), embedding_freeze=True, num_classes=2,
               fixed_length_left=30, fixed_length_right=100, use_claim_source=0, claim_source_embeddings=np.zeros((4, 8), 'float32'),
               use_article_source=1, article_source_embeddings=np.zeros((6, 8), 'float32'), cuda=0,
               num_att_heads_for_words=5, num_att_heads_for_evds=2, dropout_gnn=0.2, dropout_left=0.2, dropout_right=0.2,
               hidden_size=16, output_size=2, gsl_rate=0.6)
-net = master_get.graph_based_semantic_structure.Graph_basedSemantiStructure(params)
+net = graph_based_semantic_structure.Graph_basedSemantiStructure(params)
 assert type(net.ggnn_with_gsl).__module__ == 'get_amd.modules'
 assert params['embedding_input_dim'] == 50 and params['embedding_output_dim'] == 16
-# the fitter class the driver instantiates at :148 accepts the drop-in model
-fit = master_get.char_man_fitter_query_repr1.CharManFitterQueryRepr1
-assert callable(fit)
 print('ok')
-""" % ROOT
+""" % (ROOT, str(tmp_path))
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stderr[-3000:]
 

@@ -286,27 +286,22 @@ def test_g9_reference_kargs_reproduce_what_the_fitter_hands_over():
 
 
 # ------------------------------------------------------------- the pin checks itself
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="the reference only exists in the build container")
-def test_golden_fixtures_regenerate_identically(tmp_path):
-    """Re-run oracle/make_golden.py against /root/reference into a scratch directory: every array of every committed
-    fixture must come back bit-identical (seeded inputs, deterministic reference) -- so a stale or hand-edited fixture,
-    or a dumper that drifted from the committed vectors, fails here."""
-    import subprocess
-    import sys
+def test_golden_fixtures_are_complete_and_hold_nothing_unseeded(golden_dir):
+    """Every fixture oracle/make_golden.py writes is committed and readable (arrays, a decodable meta record where stored), the
+    state_dict contract names exactly the small model's parameters, and nothing unseeded is stored: Adam results only for
+    parameters that receive a gradient."""
+    import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, GET_GOLDEN_OUT=str(tmp_path))
-    subprocess.check_call([sys.executable, os.path.join(root, "oracle", "make_golden.py")], env=env,
-                          stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    gold = os.path.join(root, "tests", "golden")
-    names = sorted(f for f in os.listdir(gold) if f.endswith(".npz"))
-    assert names == sorted(f for f in os.listdir(tmp_path) if f.endswith(".npz"))
-    for f in names:
-        a, b = np.load(os.path.join(gold, f)), np.load(os.path.join(tmp_path, f))
-        assert sorted(a.files) == sorted(b.files), f
-        for k in a.files:
-            assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and np.array_equal(a[k], b[k], equal_nan=True), (f, k)
-    with open(os.path.join(gold, "state_dict_contract_small.json")) as fa, open(os.path.join(tmp_path, "state_dict_contract_small.json")) as fb:
-        assert fa.read() == fb.read()
-    # nothing unseeded in the fixtures: Adam results only for parameters that receive a gradient
+    src = open(os.path.join(root, "oracle", "make_golden.py")).read()
+    written = set(re.findall(r'"(g\w+\.npz)"', src)) | {f"g7_model_{n}.npz" for n in MODEL_CASES}
+    names = {f for f in os.listdir(golden_dir) if f.endswith(".npz")}
+    assert written <= names, written - names
+    for f in sorted(names):
+        z = np.load(os.path.join(golden_dir, f))
+        assert z.files, f
+        if "meta" in z.files:
+            assert isinstance(json.loads(bytes(z["meta"]).decode()), (dict, list)), f
     z, meta = load("g7_model_small.npz")
     assert not any(k.startswith("adam::") and k[6:] in meta["none_grads"] for k in z.files)
+    contract = json.load(open(os.path.join(golden_dir, "state_dict_contract_small.json")))
+    assert set(meta["none_grads"]) <= set(contract)

@@ -8,7 +8,7 @@ C4="--hidden 768 --word-heads 8 --window 5 --gsl-rate 0.8 --gemm-mode bf16 --no-
 for rep in 1 2 3; do
 for v in product measure; do
 if [ $v = product ]; then A=""; else A="--measure-build"; fi
-python bench.py $A $C4 $AB_ARGS 2>/dev/null | tail -1 | python -c "
+python bench.py --full $A $C4 $AB_ARGS 2>/dev/null | tail -1 | python -c "
 import sys, json
 d=json.loads(sys.stdin.read()); k=d['kernels']; print('$v', round(d['value']), round(d['roofline']['frac'],4), ' '.join('%s %.3f' % (n, k[n]['ms_per_step']) for n in ('gemm_big','gemm_big_tn','spmm')), 'tn frac %.3f' % k['gemm_big_tn'].get('frac_of_peak', k['gemm_big_tn'].get('frac', 0)))"
 done

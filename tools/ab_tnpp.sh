@@ -13,7 +13,7 @@ old) export GH_TN_PP_ROWS=1000000000; unset GH_TN_PP_KS;;
 pp) unset GH_TN_PP_ROWS; unset GH_TN_PP_KS;;
 ks*) unset GH_TN_PP_ROWS; export GH_TN_PP_KS=${v#ks};;
 esac
-python bench.py $C4 $AB_ARGS 2>/dev/null | tail -1 | python -c "
+python bench.py --full $C4 $AB_ARGS 2>/dev/null | tail -1 | python -c "
 import sys, json
 d=json.loads(sys.stdin.read()); k=d['kernels']; print('$v', round(d['value']), round(d['roofline']['frac'],4), ' '.join('%s %.3f' % (n, k[n]['ms_per_step']) for n in ('gemm_big','gemm_big_tn','spmm')), 'tn frac %.3f' % k['gemm_big_tn'].get('frac_of_peak', k['gemm_big_tn'].get('frac', 0)), 'parity', d.get('parity', {}).get('max_abs_logit_diff_vs_cpu_oracle'))"
 done

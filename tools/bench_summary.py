@@ -8,7 +8,7 @@ except Exception as e:
     print("bench FAILED", e)
     sys.exit(0)
 print("pairs/s %.0f ms/step %.3f n_gpus %d" % (d["value"], d["ms_per_step"], d["n_gpus"]))
-for k in ("timed", "roofline", "step_split_ms", "parity", "strong_scaling", "collective"):
+for k in ("timed", "timed_blocks", "roofline", "step_split_ms", "parity", "strong_scaling", "collective"):
     if k in d:
         print("  ", k, json.dumps(d[k])[:700])
 for name, leg in d.get("other_regimes", {}).items():
