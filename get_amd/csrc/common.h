@@ -31,9 +31,12 @@ void set_error(const char* fmt, ...);
 
 inline int words_for(int r) { return (r + 63) / 64; }
 
-// Measurement switches (environment variables GH_*: kernel-variant A/B runs, timing-only modes that skip the K loop or
-// the epilogue) exist ONLY in the tool build (`make measure` -> -DGH_MEASURE, lib/libget_hip_measure.so).  The shipped
-// library never reads the environment: a stray GH_DBG cannot turn results silently wrong.
+// A kernel variant or a tuning value is either what the product runs or it is removed (the measured-and-dropped ones live in
+// the project's history and DESIGN.md 4.5): every tuning value is a constant next to the measurement that justifies it.
+// The tool build (`make measure` -> -DGH_MEASURE, lib/libget_hip_measure.so) differs from the product only by
+// instrumentation, read from GH_* environment variables: it times or skips parts of the same kernels (GH_DBG, gemm.hip.h
+// DBG_*; GH_SPMM_DBG, GH_SPMM_MFMA_NOSTORE) or prints why a launch took a path (GH_FASTOK_DEBUG).  It never selects different
+// code.  The shipped library never reads the environment: a stray GH_DBG cannot turn results silently wrong.
 inline int measure_env(const char* name, int dflt) {
 #ifdef GH_MEASURE
   const char* e = getenv(name);

@@ -86,11 +86,15 @@ struct Launch {
   int m_tiles;   // max over problems of ceil(M / BM)
   int ksplit;    // TN: number of K chunks (1 otherwise)
   int kchunk;    // TN: rows per chunk, multiple of 16
-  int dbg;       // measurement only (GH_DBG): bit 0 = skip the epilogue, bit 1 = skip the K loop
+  int dbg;       // measurement only (tool build, GH_DBG; 0 in the product): DBG_* bits below
   int n_tiles;   // gemm_tn_pp_kernel: max over problems of ceil(N / 256) (its problems are whole outputs, not column blocks)
   int per;       // gemm_tn_pp_kernel: work items per XCD (XCD x runs items [x per, (x + 1) per) of the chunk-major list)
 };
 static_assert(sizeof(Launch) <= 4096, "Launch travels by value in the kernarg segment (4 KB)");
+// Launch::dbg bits: timing instruments of the tool build (common.h GH_DBG_BITS).  They skip or time parts of the same kernels.
+constexpr int DBG_NO_EPILOGUE = 1;      // K loop only
+constexpr int DBG_NO_KLOOP = 2;         // epilogue only (one K tile)
+constexpr int DBG_EPI_TICKS = 1024;     // 256-tile epilogue: per-kind tick sums into g_nt_phase (gh_debug_nt_phases)
 
 __host__ __device__ __forceinline__ unsigned drop_hash(unsigned seed, unsigned idx) {
   unsigned x = idx * 0x9E3779B1u + seed;

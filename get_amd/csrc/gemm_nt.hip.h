@@ -67,7 +67,7 @@ __device__ __forceinline__ unsigned nt_pack_bf16(float a, float b) {
 template <int WM, int WN, int NI, int MI = 2, int MODE = 0>
 // (second argument = waves per SIMD the register budget must allow: 256-thread workgroups put one wave on every SIMD, so it is also
 //  the workgroups per CU; the 512-thread 128 x 256 tile puts two, and wants two workgroups = four waves per SIMD)
-__global__ void __launch_bounds__(WM * WN * 64, (MI == 8) ? 2 : (WM == 4 && WN == 2 && NI == 5 && MI == 2) ? 4 : (MI == 4 && NI == 4 && WN == 4) ? 4 : (MI == 4 && NI == 4) ? 3 : (MI == 4 || MODE == 3 || MODE == 4) ? 2 : (WM == 2 && WN == 2 && NI == 5 && MODE == 0) ? 4 : 3)
+__global__ void __launch_bounds__(WM * WN * 64, (MI == 8 || MI == 4 || MODE == 3 || MODE == 4) ? 2 : (WM == 2 && WN == 2 && NI == 5 && MODE == 0) ? 4 : 3)
 gemm_nt_kernel(const Launch L_byval) {
   (void)L_byval;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -80,9 +80,6 @@ gemm_nt_kernel(const Launch L_byval) {
   // below (PP) -- the two wave rows run staggered by one barrier interval, so that each SIMD always has one wave in its
   // MFMA section and one reading fragments / issuing LDS-DMA.
   constexpr bool PP = MI == 8;
-  constexpr bool PP32_ = MODE == 0 && WM == 4 && WN == 2 && NI == 5 && MI == 2;
-  // <4, 2, 5, 2, 0>: the exact-fp32 128 x 160 x 16 tile on 8 waves, two workgroups per CU, ping-pong K loop (gemm_nt_pp32.hip.h)
-  constexpr bool PP32 = MODE == 0 && WM == 4 && WN == 2 && NI == 5 && MI == 2;
   constexpr int BM = 16 * MI * WM, BN = 16 * NI * WN, BK = PP ? 64 : 4 * KQ;
   // MODE 4 ("fp32x3" with PRE-SPLIT weights): B points at the weight's split image (split3_kernel: per row and group
   // of four k the three bf16 pieces hi[4] | mid[4] | lo[4], 24 bytes; row pitch a multiple of 16 bytes, passed as ldb in
@@ -102,9 +99,9 @@ gemm_nt_kernel(const Launch L_byval) {
   // newest tile's DMA as well).  73.5 KB of LDS -> dynamic allocation.
   // (fp32x3, MODE 3, measured with three stages as well: slower -- 122 vs 132 TF at K = 1200 -- its K loop is bound by the
   // VALU work of the in-register splits, not by DMA latency)
-  constexpr int NST = (MI == 4 && WM == 4) ? 4 : (MI == 4) ? 3 : 2;      // (256 x 256 / 8 waves: one workgroup per CU, four stages)
+  constexpr int NST = MI == 4 ? 3 : 2;
   constexpr bool DYN_LDS = NST != 2 || X3P || PP;                        // more than 64 KB: dynamic allocation
-  constexpr int SMEM = PP ? 131072 : PP32_ ? (3 * STAGE + 1024 > EP_BYTES ? 3 * STAGE + 1024 : EP_BYTES) : (NST * STAGE > EP_BYTES ? NST * STAGE : EP_BYTES);
+  constexpr int SMEM = PP ? 131072 : (NST * STAGE > EP_BYTES ? NST * STAGE : EP_BYTES);
   static_assert(!PP || (MODE == 2 && WM == 2 && WN == 4 && NI == 4 && EP_BYTES <= 131072), "ping-pong loop: 256 x 256 bf16 tile on 2 x 4 waves");
   constexpr unsigned OOB = 0x80000000u;
   constexpr int NH = NI / 2;                                       // B fragment batches: X = tiles [0,NH), Y = [NH,NI)
@@ -120,7 +117,7 @@ gemm_nt_kernel(const Launch L_byval) {
   // (few-row launches -- fewer than 8 row tiles, e.g. the head's 32-row split-K products: the grid is m_tiles x n_inner and
   //  consecutive workgroups, i.e. the 8 XCDs, take the (problem, K chunk) units of ONE row tile; the row-tile-per-XCD deal
   //  would leave every workgroup of a one-row-tile launch on XCD 0)
-  const bool few = L.m_tiles < 8 && !(GH_DBG_BITS(L) & 32);
+  const bool few = L.m_tiles < 8;
   const int m_tile = few ? bid / n_inner : xcd + 8 * (slot / n_inner);
   const int inner = few ? bid % n_inner : slot % n_inner;
   if (m_tile >= L.m_tiles) return;
@@ -132,16 +129,7 @@ gemm_nt_kernel(const Launch L_byval) {
   const int m0 = m_tile * BM;
   if (m0 >= M) return;
 
-  // measurement switches (tool build only, common.h): static wave priority per workgroup class, so that co-resident
-  // workgroups drift out of phase
-  const int dbg_bits = GH_DBG_BITS(L);
-  if (dbg_bits & 4) {
-    const int cls = ((bid >> 3) >> 5) % 3;
-    if (cls == 0) __builtin_amdgcn_s_setprio(2); else if (cls == 1) __builtin_amdgcn_s_setprio(1);
-  } else if (dbg_bits & 8) {
-    const int cls = (bid >> 3) % 3;
-    if (cls == 0) __builtin_amdgcn_s_setprio(2); else if (cls == 1) __builtin_amdgcn_s_setprio(1);
-  }
+  const int dbg_bits = GH_DBG_BITS(L);      // (tool build only, common.h: DBG_* timing modes)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
@@ -163,7 +151,7 @@ gemm_nt_kernel(const Launch L_byval) {
   // the node-compact layout): start at the first tile of segment 1
   const int toff = (nseg > 1 && P.seg0_rows > 0 && m0 >= P.seg0_rows && !split) ? nt0 : 0;
   const int T_all = nt0 + (nseg > 1 ? (K1 + BK - 1) / BK : 0) - toff;
-  int tbeg = 0, tend = (dbg_bits & 2) ? 1 : T_all;
+  int tbeg = 0, tend = (dbg_bits & DBG_NO_KLOOP) ? 1 : T_all;
   if (split) {
     const int ct = L.kchunk / BK;
     tbeg = ks * ct;
@@ -344,11 +332,7 @@ gemm_nt_kernel(const Launch L_byval) {
   };
   // column tiles of this wave that hold at least one real column (N = 300: the last wave column has 9 of 10); the B
   // rows beyond N are zero in LDS, so skipping their MFMAs changes nothing but the time.  Wave-uniform.
-#ifdef GH_NT_NOSKIP
-  const int nv = NI;
-#else
   const int nv = min(NI, max(0, (N - wcol + 15) >> 4));
-#endif
   const int nvX = min(NH, nv), nvY = nv - nvX;
   auto mma = [&](const f32x4* a, const f32x4* b, int ni0, auto CNT) __attribute__((always_inline)) { mma_n(a, b, ni0, CNT); };
   // stateless input dropout (wrapper.py:189-190) on the A fragments of segment 0: element (row, k) of [rows][drop_ld]
@@ -556,8 +540,6 @@ gemm_nt_kernel(const Launch L_byval) {
   // (any other count -- narrow problems, odd column blocks -- computes every tile: the B rows beyond N are zeros in LDS)
   if constexpr (PP) {
 #include "gemm_nt_pp.hip.h"
-  } else if constexpr (PP32) {
-#include "gemm_nt_pp32.hip.h"
   } else {
     if (nvX == NH && nvY == NI - NH - 1) run(std::integral_constant<int, NH>{}, std::integral_constant<int, NI - NH - 1>{});
     else run(std::integral_constant<int, NH>{}, std::integral_constant<int, NI - NH>{});
@@ -568,7 +550,7 @@ gemm_nt_kernel(const Launch L_byval) {
   // is float4 (row i / C4, column chunk i % C4) with C4 = EP_PITCH/4 a compile-time divisor, so a wave instruction
   // touches one contiguous run of a row in every epilogue stream.  Row reductions (attention head scores, the GSL
   // scorer's projection) read the finished rows back from LDS, one wave per row, in a fixed order (deterministic).
-  if (dbg_bits & 1) {      // (tool build: K loop only.  Every accumulator stays live -- a test of two of them lets the compiler drop the other MFMAs)
+  if (dbg_bits & DBG_NO_EPILOGUE) {      // (tool build: K loop only.  Every accumulator stays live -- a test of two of them lets the compiler drop the other MFMAs)
     float sum = 0.f;
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
@@ -587,7 +569,7 @@ gemm_nt_kernel(const Launch L_byval) {
   const int accumulate = P.accumulate;
   const int heads = P.heads;
   const bool scorer = (epi == EPI_TANH_H) && (P.w2 != nullptr);
-  const int pad_rows = (MODE == 2 || (dbg_bits & 64)) ? 0 : P.seg0_rows;                    // first padding row of the node-compact layout (0: none)
+  const int pad_rows = MODE == 2 ? 0 : P.seg0_rows;                    // first padding row of the node-compact layout (0: none)
   const bool out_dead = scorer && P.ldu == 1;                            // EPI_TANH_H: padding rows' outputs feed the scorer only
   const bool rowred = (epi == EPI_ATT) || scorer;
   float* ep = reinterpret_cast<float*>(smem);
@@ -627,8 +609,7 @@ gemm_nt_kernel(const Launch L_byval) {
     // streaming (nontemporal) stores: an epilogue output is ~75 MB that the next launch reads from the start; keeping its
     // tail in L2 only evicts the weight panels the K loops are re-reading (A/B on the bench step: +0.4 %; nontemporal LOADS
     // of the epilogue inputs: no change)
-    if (!(dbg_bits & 16)) { __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4*>(p + o)); return; }
-    *reinterpret_cast<float4*>(p + o) = v;
+    __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4*>(p + o));
   };
   auto row_reduce = [&](auto MIT) __attribute__((always_inline)) {
     constexpr int mi = decltype(MIT)::value;
@@ -682,10 +663,7 @@ gemm_nt_kernel(const Launch L_byval) {
     // pointers may alias as far as the compiler knows, so a plain loop would serialise 11 memory round trips per pass.
     auto pass = [&](auto EPI) __attribute__((always_inline)) {
       constexpr int E = decltype(EPI)::value;
-#ifndef GH_EPI_CH
-#define GH_EPI_CH 4
-#endif
-      constexpr int CH = GH_EPI_CH;
+      constexpr int CH = 4;
 #pragma unroll
       for (int it0 = 0; it0 < NIT; it0 += CH) {
         float4 xa[CH], xb[CH], xc[CH], xd[E == EPI_GATE_PRE ? CH : 1];

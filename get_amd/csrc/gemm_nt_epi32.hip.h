@@ -13,10 +13,7 @@
 {
   constexpr int NITF = (ITEMS + NTHR - 1) / NTHR;      // items per thread and pass
   constexpr int TOT = MI * NITF;
-#ifndef GH_E32_PD
-#define GH_E32_PD 2
-#endif
-  constexpr int PD = GH_E32_PD, NSET = PD + 1;      // prefetch distance in items, register sets
+  constexpr int PD = 2, NSET = PD + 1;      // prefetch distance in items, register sets
   typedef unsigned e32_u32x4 __attribute__((ext_vector_type(4)));
   // (the thread id through an opaque move: without it the compiler hoists the items' address arithmetic -- loop invariant as far
   //  as it can see -- above the K loop, where ~60 live values spill inside the MFMA stream)
@@ -156,13 +153,9 @@
       constexpr int idx = decltype(IDX)::value;
       if constexpr (idx % NITF == 0) stage(std::integral_constant<int, idx / NITF>{});
       if constexpr (idx + PD < TOT) load(std::integral_constant<int, idx + PD>{});
-#ifndef GH_E32_NOSB
       __builtin_amdgcn_sched_barrier(0);      // (pin the order of the items)
-#endif
       compute(IDX);
-#ifndef GH_E32_NOSB
       __builtin_amdgcn_sched_barrier(0);
-#endif
       if constexpr (idx % NITF == NITF - 1) { if (rowred) row_reduce(std::integral_constant<int, idx / NITF>{}); }
     };
     load(std::integral_constant<int, 0>{});
@@ -177,7 +170,7 @@
   };
   constexpr std::integral_constant<bool, false> NO{};
   constexpr std::integral_constant<bool, true> YES{};
-  if (!(dbg_bits & 128) && io == 0) {
+  if (io == 0) {
     f32_done = true;
     if (epi == EPI_STORE) { if (accumulate) fast(std::integral_constant<int, EPI_STORE>{}, YES, NO); else fast(std::integral_constant<int, EPI_STORE>{}, NO, NO); }
     else if (epi == EPI_SIGMOID_Z) fast(std::integral_constant<int, EPI_SIGMOID_Z>{}, NO, NO);

@@ -93,11 +93,7 @@
     // pass p + 1 requested only one pass (~2.5 us) ahead, every pass still waited for its loads.  Kinds whose inputs are few registers
     // therefore request them further ahead: PD passes, PD + 1 register sets of 2 items x (input streams) x 16 B.
     constexpr int PER_SET = 2 * (NIN + ((GIN || ATT) ? 2 : 0));      // 16-byte registers per set
-#ifdef GH_PP_PD
-    constexpr int PD = PER_SET == 0 ? 1 : (GH_PP_PD);
-#else
     constexpr int PD = PER_SET == 0 ? 1 : PER_SET <= 2 ? 2 : 1;
-#endif
     constexpr int NSET = PD + 1;
     pp_u32x4 ra[NSET][2], rb[NSET][2], rc[NSET][2], rg[NSET][2][2];      // [register set][item]; gin: two 16-byte halves of eight fp32
     float4 sw0 = make_float4(0.f, 0.f, 0.f, 0.f), sw1 = sw0;
@@ -237,7 +233,7 @@
     auto pass = [&](auto PT) __attribute__((always_inline)) {
       constexpr int p_ = decltype(PT)::value;
 #ifdef GH_MEASURE
-      const bool ticks = (dbg_bits & 1024) != 0;      // GH_DBG=1024: per-kind tick sums (costs atomics: not for timing runs)
+      const bool ticks = (dbg_bits & DBG_EPI_TICKS) != 0;      // per-kind tick sums (costs atomics: not for timing runs)
       const unsigned long long tp0 = ticks ? __builtin_amdgcn_s_memtime() : 0ull;
 #endif
       pp_stage(PT);
@@ -269,7 +265,7 @@
     constexpr std::integral_constant<bool, false> NO{};
     constexpr std::integral_constant<bool, true> YES{};
     const bool no_c32 = c32 == nullptr;
-    if (!(dbg_bits & 128) && no_c32) {
+    if (no_c32) {
       if (epi == EPI_ATT && pp_io == 0) { pp_fast(std::integral_constant<int, EPI_ATT>{}, NO, NO, NO); return; }
       if (epi == EPI_STORE && (pp_io & 1)) {
         if (accumulate) pp_fast(std::integral_constant<int, EPI_STORE>{}, YES, NO, NO); else pp_fast(std::integral_constant<int, EPI_STORE>{}, NO, NO, NO);
@@ -278,7 +274,7 @@
       if (epi == EPI_SIGMOID_Z && (pp_io & 1)) { pp_fast(std::integral_constant<int, EPI_SIGMOID_Z>{}, NO, NO, NO); return; }
       if (epi == EPI_SIGMOID_R && (pp_io & 7) == 7) { pp_fast(std::integral_constant<int, EPI_SIGMOID_R>{}, NO, NO, NO); return; }
       if (epi == EPI_TANH_H && (pp_io & 15) == 15) {
-        if (scorer && P.e_atomic != 1 && !(dbg_bits & 512)) pp_fast(std::integral_constant<int, EPI_TANH_H>{}, NO, NO, YES);
+        if (scorer && P.e_atomic != 1) pp_fast(std::integral_constant<int, EPI_TANH_H>{}, NO, NO, YES);
         else pp_fast(std::integral_constant<int, EPI_TANH_H>{}, NO, NO, NO);
         return;
       }

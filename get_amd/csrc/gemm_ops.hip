@@ -14,10 +14,12 @@ static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) 
 
 static bool s_lds_bad(const Problem& p) { return p.seg[0].lda % 8 || p.seg[0].ldb % 8; }
 // fast-path preconditions of gemm_nt.hip.h (NT: both operands contraction-contiguous) and gemm_tn.hip.h (TN); both LDS-DMA
-static void fast_why(int rule, int prob) {      // tool build: GH_FASTOK_DEBUG=1 names the rule that sent a launch to the generic kernel
-  static int dbg = -1;
-  if (dbg < 0) dbg = measure_env("GH_FASTOK_DEBUG", 0);
-  if (dbg) fprintf(stderr, "gemm: generic kernel (fast_ok rule %d, problem %d)\n", rule, prob);
+// tool build: GH_FASTOK_DEBUG=1 names the rule that sent a launch to the generic kernel (seg >= 0: and that segment's sizes)
+static void fast_why(int rule, int prob, const Problem* p = nullptr, int seg = -1) {
+  static const bool dbg = measure_env("GH_FASTOK_DEBUG", 0) != 0;
+  if (!dbg) return;
+  fprintf(stderr, "gemm: generic kernel (fast_ok rule %d, problem %d)\n", rule, prob);
+  if (p && seg >= 0) fprintf(stderr, "   seg %d lda %d M %d N %d K %d\n", seg, p->seg[seg].lda, p->M, p->N, p->seg[seg].K);
 }
 static bool fast_ok(const Launch& L, bool tn) {
   for (int i = 0; i < L.nprob; ++i) {
@@ -32,7 +34,7 @@ static bool fast_ok(const Launch& L, bool tn) {
     if (!tn) {  // operands are addressed through buffer descriptors: 31-bit byte offsets
       for (int j = 0; j < p.nseg; ++j) {
         if (4.0 * (double)p.seg[j].ldb * (double)p.N >= 2147483648.0) { fast_why(4, i); return false; }
-        if (!p.seg[j].gatherA && 4.0 * (double)p.seg[j].lda * (double)p.M >= 2147483648.0) { fast_why(5, i); if (measure_env("GH_FASTOK_DEBUG", 0)) fprintf(stderr, "   seg %d lda %d M %d N %d K %d\n", j, p.seg[j].lda, p.M, p.N, p.seg[j].K); return false; }   // (gathered tables: < 2 GB by contract)
+        if (!p.seg[j].gatherA && 4.0 * (double)p.seg[j].lda * (double)p.M >= 2147483648.0) { fast_why(5, i, &p, j); return false; }   // (gathered tables: < 2 GB by contract)
       }
     }
     if (tn) {
@@ -50,19 +52,9 @@ static bool fast_ok(const Launch& L, bool tn) {
   }
   return true;
 }
-// bf16 weight-gradient GEMM on 128 x 320 tiles (gemm_tn_bf16_kernel<2, 2, 10, 4>; tool build: GH_TN16_TALL=0 restores 64 x 320)
-static bool tn16_tall() {
-  static int v = -1;
-  if (v < 0) v = measure_env("GH_TN16_TALL", 1);
-  return v != 0;
-}
 // bf16 weight-gradient GEMM on the 256 x 256 x 64 ping-pong tile (gemm_tn_pp.hip.h): K-chunk rows from which a batch of whole-output
-// problems takes it (tool build: GH_TN_PP_ROWS; a huge value restores the 128 x 320 kernel everywhere)
-static int tn_pp_rows() {
-  static int v = -1;
-  if (v < 0) v = measure_env("GH_TN_PP_ROWS", 16384);
-  return v;
-}
+// problems takes it (below: the 128 x 320 tile, gemm_tn_bf16_kernel<2, 2, 10, 4>)
+constexpr int TN_PP_ROWS = 16384;
 static bool wants_dropout(const Launch& L) {
   for (int i = 0; i < L.nprob; ++i)
     if (L.p[i].drop_mode) return true;
@@ -80,12 +72,6 @@ static bool x3p_substitute(Launch& L, hipStream_t s);
 
 int gemm_mode() { return g_gemm_mode; }
 
-static bool few_row_bf16() {
-  static int v = -1;
-  if (v < 0) v = measure_env("GH_FEW_BF16", 1);
-  return v != 0;
-}
-
 template <int WM, int WN, int NI, int MI = 2>
 static hipError_t launch_cfg(const Launch& L, bool tn, hipStream_t s) {
   const bool fast = fast_ok(L, tn);
@@ -98,7 +84,7 @@ static hipError_t launch_cfg(const Launch& L, bool tn, hipStream_t s) {
   }
   const int n_outer = tn ? L.ksplit : L.m_tiles;
   const int n_inner = tn ? L.m_tiles * L.nprob : L.nprob * L.ksplit;
-  const bool nt_few = !tn && L.m_tiles < 8 && fast && !(GH_DBG_BITS(L) & 32);      // gemm_nt.hip.h: linear work decode for launches of fewer than 8 row tiles
+  const bool nt_few = !tn && L.m_tiles < 8 && fast;      // gemm_nt.hip.h: linear work decode for launches of fewer than 8 row tiles
   const int grid = nt_few ? n_outer * n_inner : 8 * ((n_outer + 7) / 8) * n_inner;
   if (grid <= 0) return hipSuccess;
   // profiler row: by the SIZE of the launch, not by the tile configuration it runs on -- the activation-sized single-problem
@@ -131,10 +117,7 @@ static hipError_t launch_cfg(const Launch& L, bool tn, hipStream_t s) {
   if (any_elt) {      // bf16 storage pipeline: only on the 64x320 fast kernels, never mixed with fp32 problems
     if (!fast || !all_elt) return hipErrorInvalidValue;
     if constexpr (WM == 2 && WN == 2 && NI == 10) {
-      if (tn) {
-        if (tn16_tall()) hipLaunchKernelGGL((gemm_tn_bf16_kernel<2, 2, 10, 4>), dim3(grid), dim3(256), 0, s, L);
-        else hipLaunchKernelGGL((gemm_tn_bf16_kernel<2, 2, 10>), dim3(grid), dim3(256), 0, s, L);
-      }
+      if (tn) hipLaunchKernelGGL((gemm_tn_bf16_kernel<2, 2, 10, 4>), dim3(grid), dim3(256), 0, s, L);      // (128 x 320 tile)
       else hipLaunchKernelGGL((gemm_nt_kernel<2, 2, 10, 2, 2>), dim3(grid), dim3(256), 0, s, L);
       launched = true;
     } else if constexpr (WM == 2 && WN == 2 && NI == 8 && MI == 4) {      // 128 x 256 tile (NT only)
@@ -143,13 +126,6 @@ static hipError_t launch_cfg(const Launch& L, bool tn, hipStream_t s) {
       static bool attr = false;
       if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<2, 2, 8, 4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds); attr = true; }
       hipLaunchKernelGGL((gemm_nt_kernel<2, 2, 8, 4, 2>), dim3(grid), dim3(256), kLds, s, L);
-      launched = true;
-    } else if constexpr (WM == 2 && WN == 2 && NI == 4 && MI == 4) {      // 128 x 128 tile, three workgroups per CU (NT only)
-      if (tn) return hipErrorInvalidValue;
-      constexpr int kLds = 3 * (128 + 128) * 64;
-      static bool attr = false;
-      if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<2, 2, 4, 4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds); attr = true; }
-      hipLaunchKernelGGL((gemm_nt_kernel<2, 2, 4, 4, 2>), dim3(grid), dim3(256), kLds, s, L);
       launched = true;
     } else if constexpr (WM == 2 && WN == 4 && NI == 4 && MI == 8) {      // 256 x 256 x 64 tile, 8 waves, ping-pong K loop (NT only; gemm_nt_pp.hip.h)
       if (tn) return hipErrorInvalidValue;
@@ -171,14 +147,11 @@ static hipError_t launch_cfg(const Launch& L, bool tn, hipStream_t s) {
     if (g_gemm_mode == 1 && WM == 2 && WN == 2 && NI == 10) {
       if constexpr (WM == 2 && WN == 2 && NI == 10)
         hipLaunchKernelGGL((gemm_nt_kernel<2, 2, 10, 2, true>), dim3(grid), dim3(256), 0, s, L);
-    } else if (g_gemm_mode == 1 && WM == 1 && WN == 4 && NI == 5 && few_row_bf16()) {
+    } else if (g_gemm_mode == 1 && WM == 1 && WN == 4 && NI == 5) {
       // ... and in the few-row launches (32 x 320 tile): at h = 768 the evidence-level products (960 rows against 22 / 41 MB
       // weights) and the claim cell are 0.5 ms of fp32 MFMA time per step
       if constexpr (WM == 1 && WN == 4 && NI == 5)
         hipLaunchKernelGGL((gemm_nt_kernel<1, 4, 5, 2, true>), dim3(grid), dim3(256), 0, s, L);
-    } else if constexpr (WM == 4) {      // the ping-pong fp32 tile exists in the exact mode only (Batch sets pp32 for g_gemm_mode == 0)
-      if (g_gemm_mode != 0) return hipErrorInvalidValue;
-      hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, NI, 2>), dim3(grid), dim3(WM * WN * 64), 0, s, L);
     } else if (g_gemm_mode == 2 || g_gemm_mode == 3) {      // fp32x3 (experimental): fp32 values and results, products from 3-way bf16 splits on the bf16 MFMA
       Launch L2;
       bool pre = false;
@@ -559,11 +532,8 @@ struct Batch {
   // the K loops: launches with stream-heavy epilogues gain, plain-store launches lose (prototype, tools/glds_proto.hip NHALF:
   // h-gate-like epilogue K = 300: 62.6 -> 68.2 TF, K = 600: 87.7 -> 90.5; plain store: 92.4 -> 88.7).  Chosen per call site.
   bool narrow = false;
-  // 128 x 160 fp32 tile, 8 waves, two workgroups per CU, ping-pong K loop (launch_cfg<4, 2, 5>; gemm_nt_pp32.hip.h).  TOOL BUILD ONLY
-  // (GH_PP32_ROWS): built in round 6 as the fp32 half of VERDICT r5 item 1 and measured SLOWER than the 64 x 320 / 64 x 160 tiles at three
-  // / four workgroups per CU: K loops alone 3.37 against 3.15 ms per step, whole launches 3.98 against 3.72 (two and three LDS buffers
-  // alike; a half-K-loop start stagger of each CU's second workgroup: no effect at any amount).  DESIGN 4.5.
-  bool pp32 = false;
+  // (round 6: a 128 x 160 fp32 tile on 8 waves with a ping-pong K loop measured SLOWER than the 64 x 320 / 64 x 160 tiles at three / four
+  //  workgroups per CU: K loops alone 3.37 against 3.15 ms per step, whole launches 3.98 against 3.72.  Removed)
   // EPI_ATT on rows wider than one column block (h = 768): every block applies tanh(. + u) to its columns and reduces ITS share
   // of the head scores W2 . t into a partial buffer of its own, e + block * e_block_stride (plain stores: the consumer,
   // att_softmax_fwd, adds the partials in block order -- deterministic).  0 = whole rows only.
@@ -576,56 +546,36 @@ struct Batch {
   bool tn_pp_ok(const Problem& p) const {
     if (!tn || !p.elt || p.nseg != 1 || g_ws == nullptr || p.epi != EPI_ATOMIC) return false;
     const Seg& sg = p.seg[0];
-    if (sg.gatherA || sg.gatherB || !sg.vecA || !sg.vecB || sg.K < tn_pp_rows()) return false;
+    if (sg.gatherA || sg.gatherB || !sg.vecA || !sg.vecB || sg.K < TN_PP_ROWS) return false;
     if (p.M % 256 || p.N % 256 || p.ldc % 4 || (reinterpret_cast<uintptr_t>(p.C) & 15)) return false;
     return (size_t)sg.K * (size_t)sg.lda * 2 < ((size_t)1 << 31) && (size_t)sg.K * (size_t)sg.ldb * 2 < ((size_t)1 << 31);
   }
-  bool wide128 = false;   // 128 x 128 bf16 tile, three workgroups per CU (launch_cfg<2, 2, 4, 4>; tool build: GH_BF16_TILE=128)
   // (round 5: the same 128 x 256 tile on EIGHT waves -- 64 x 64 per wave, two workgroups = four waves per SIMD -- needs 146 VGPRs
   //  for its 128-register budget: 82 spills, 16 instead of 12 ds_read_b128 per 32 MFMAs; configs[4] bf16 115.3 -> 99.6 K pairs/s. Removed.)
   // wide_bf16: every problem of this batch is a bf16-storage NT problem whose widths are multiples of 256 (h = 768)
-  // site: 0 = never narrow; 1.. = call site id, narrow when the site's bit is set in the mask (tool build: GH_NT_NARROW)
+  // site: 0 = never narrow; 1.. = call site id, narrow when the site's bit is set in NARROW_DEFAULT
   // n_hint: output width of the site's problems -- widths that 160-column blocks cover with less padding than 320-column
   // blocks (h = 768: 800 against 960 computed columns) take the narrow tile at every site (configs[4] in fp32: 26.1 -> 28.4 K pairs/s)
   Batch(bool tn_, int rows_hint, hipStream_t s_, bool wide_bf16 = false, int site = 0, int n_hint = 0) : tn(tn_), s(s_) {
     const Workspace w = workspace_for(s_);
     g_ws = w.p; g_ws_bytes = w.bytes;
-    static int force_small = -1;
-    if (force_small < 0) force_small = measure_env("GH_NT_FORCE_SMALL", 0);
-    big = tn_ || (rows_hint >= 8192 && !force_small);      // 64x320 tile (2x2 waves) for the activation-sized GEMMs, 32x320 (1x4) for few-row ones
+    big = tn_ || rows_hint >= 8192;      // 64x320 tile (2x2 waves) for the activation-sized GEMMs, 32x320 (1x4) for few-row ones
     bm = big ? 64 : 32;
     bn = 320;
-    static int no_wide = -1;
-    if (no_wide < 0) no_wide = measure_env("GH_BF16_TILE", 0) == 320 ? 1 : 0;
-    if (wide_bf16 && big && !tn_ && !no_wide) { wide = true; bm = 128; bn = 256; }
+    if (wide_bf16 && big && !tn_) { wide = true; bm = 128; bn = 256; }
     // 256 x 256 x 64 / 8 waves, one workgroup per CU, ping-pong K loop + software-pipelined epilogue (gemm_nt_pp.hip.h, round 6):
     // the default for activation-sized launches of the bf16 storage pipeline -- configs[4], B = 32: gemm_big 4.25 -> 3.09 ms per
     // step, 128.1 -> 148.6 K pairs/s.  (Round 3's 256 x 256 tile -- the 128 x 256 tile's K loop on 8 waves, 32-deep stages --
     // measured 0.200 against 0.207: not the tile size but the loop structure is the lever.)  Launches below 32 768 rows (fewer
-    // than 1.5 workgroups per CU) keep the 128 x 256 tile.  Tool build: GH_BF16_TILE=1 restores 128 x 256 everywhere,
-    // GH_BF16_TILE256_ROWS moves the row threshold.
-    static int tile_env = -1;
-    if (tile_env < 0) tile_env = measure_env("GH_BF16_TILE", 0);
-    static int tile256_rows = -1;
-    if (tile256_rows < 0) tile256_rows = measure_env("GH_BF16_TILE256_ROWS", 32768);
-    if (wide && rows_hint >= tile256_rows && tile_env != 1 && tile_env != 128) { wide256 = true; bm = 256; }
-    static int tile128 = -1;
-    if (tile128 < 0) tile128 = measure_env("GH_BF16_TILE", 0) == 128 ? 1 : 0;
-    if (wide && tile128) { wide128 = true; bn = 128; }
-    static int narrow_mask = -1;
-    if (narrow_mask < 0) narrow_mask = measure_env("GH_NT_NARROW", NARROW_DEFAULT);
+    // than 1.5 workgroups per CU) keep the 128 x 256 tile.
+    constexpr int tile256_rows = 32768;
+    if (wide && rows_hint >= tile256_rows) { wide256 = true; bm = 256; }
     const bool less_pad = n_hint > 0 && (n_hint + 159) / 160 * 160 < (n_hint + 319) / 320 * 320;
     // launches whose 64 x 320 grid would not fill one round of 768 workgroup slots (realistic evidence counts: 14 208 rows = 222
     // row tiles) get twice the workgroups on 1024 slots: 99.0 -> 102.0 K pairs/s on the Snopes-histogram step at B = 32
     const bool thin = rows_hint <= 24576;
-    if (site > 0 && big && !tn_ && !wide && g_gemm_mode == 0 && narrow_mask != 0 && (((narrow_mask >> (site - 1)) & 1) || less_pad || thin)) { narrow = true; bn = 160; }
-    static int pp32_rows = -1;
-    if (pp32_rows < 0) pp32_rows = measure_env("GH_PP32_ROWS", 1 << 30);      // (tool build: row threshold of the fp32 ping-pong tile)
-    // (`narrow` stays set: the call sites' column-block logic -- two 160-wide blocks per 300-wide problem, the scorer's two partial dot
-    //  products -- is the 64 x 160 tile's; launches without a call-site id, e.g. the attention's t product with its head scores, keep the 64 x 320 tile)
-#ifdef GH_MEASURE
-    if (site > 0 && big && !tn_ && !wide && g_gemm_mode == 0 && rows_hint >= pp32_rows) { pp32 = true; narrow = true; bm = 128; bn = 160; }
-#endif
+    if (site > 0 && big && !tn_ && !wide && g_gemm_mode == 0 && (((NARROW_DEFAULT >> (site - 1)) & 1) || less_pad || thin)) { narrow = true; bn = 160; }
+    // (launches without a call-site id, e.g. the attention's t product with its head scores, keep the 64 x 320 tile)
     // (round 5: thin launches on 32 x 160 tiles -- one 16-row MFMA tile per wave, 80 - 96 VGPRs, five or six workgroups per CU, twice
     //  the waves for grids that fill less than one round -- measured on the Snopes-count step: 109.4 K -> 108.2 - 109.4 K pairs/s
     //  at every site mask.  Removed.)
@@ -633,8 +583,7 @@ struct Batch {
   }
   void reset() {
     L.nprob = 0; L.m_tiles = 0; L.ksplit = 1; L.kchunk = 0; k_total = 0; L.n_tiles = 0; L.per = 0;
-    static int dbg = -1;
-    if (dbg < 0) dbg = measure_env("GH_DBG", 0);
+    static const int dbg = measure_env("GH_DBG", 0);      // (tool build: DBG_* bits, gemm.hip.h)
     L.dbg = dbg;
     for (int i = 0; i < GH_MAX_PROBLEMS; ++i) cs_out[i] = cs_out2[i] = nullptr;
   }
@@ -681,7 +630,7 @@ struct Batch {
       if (att_blocks) { q.w2 += n0; q.u += n0; q.e = p.e + (size_t)(n0 / bn) * (size_t)e_block_stride; q.e_atomic = 2; }      // (2: own partial buffer, plain stores)
       if (L.nprob == GH_MAX_PROBLEMS) flush();
       L.p[L.nprob++] = q;
-      const int bm_eff = tn_pp ? 256 : (tn && q.elt && tn16_tall()) ? 128 : bm;      // (all problems of a TN launch share the storage mode)
+      const int bm_eff = tn_pp ? 256 : (tn && q.elt) ? 128 : bm;      // (bf16 TN: the 128 x 320 tile; all problems of a TN launch share the storage mode)
       const int mt = (q.M + bm_eff - 1) / bm_eff;
       if (mt > L.m_tiles) L.m_tiles = mt;
       if (tn_pp && (q.N + 255) / 256 > L.n_tiles) L.n_tiles = (q.N + 255) / 256;
@@ -693,14 +642,12 @@ struct Batch {
     if (L.nprob == 0 || err != hipSuccess) { reset(); return; }
     if (tn) {
       const int n_inner = L.m_tiles * L.nprob;
-      static int target = -1;
-      if (target < 0) target = measure_env("GH_TN_SPLIT_TARGET", 2304);
+      constexpr int target = 2304;
       int ks = (target + n_inner - 1) / n_inner;   // three resident rounds of 256 CUs x 3 workgroups (measured on the bench step: 1152 -> 2.06 ms,
                                                    // 1536 -> 1.95, 2304 -> 1.86, 3072 -> 1.84 but more partials to reduce; one round 20 % slower)
       // shortest K chunk: 256 rows (fp32).  bf16 storage, wide outputs (h = 768: 64 x 320 partial tiles of 80 KB each): a single
       // 768 x 768 product split into 64 chunks writes and re-reads more partial-tile bytes than it streams operands
-      static int min_rows16 = -1;
-      if (min_rows16 < 0) min_rows16 = measure_env("GH_TN_MIN_ROWS16", 4096);      // (A/B on configs[4]: 256 / 1024 / 2048 / 4096 rows = 106.76 / 106.72 / 106.81 / 107.17 K pairs/s)
+      constexpr int min_rows16 = 4096;      // (A/B on configs[4]: 256 / 1024 / 2048 / 4096 rows = 106.76 / 106.72 / 106.81 / 107.17 K pairs/s)
       const int min_rows = L.p[0].elt ? min_rows16 : 256;
       const int ks_max = (k_total / min_rows > 1) ? k_total / min_rows : 1;
       if (ks > ks_max) ks = ks_max;
@@ -708,8 +655,6 @@ struct Batch {
       // The K chunks are dealt round-robin to the 8 XCDs (chunk c runs on XCD c % 8, gemm_tn.hip.h): a chunk count that is
       // not a multiple of 8 leaves some XCDs one chunk (1 / 8 of their work at 65 chunks) more than the others.  Measured on
       // the bench step (A/B, one box): 65 chunks 158.6 K pairs/s, 72 chunks 159.9 K, 85 chunks 156.4 K.
-      static int xcd_rule = -1;
-      if (xcd_rule < 0) xcd_rule = measure_env("GH_TN_XCD_RULE", 1);
       const int align = tn_pp ? 64 : L.p[0].elt ? 32 : 16;      // K tile of the kernel (bf16 storage: 32 rows, ping-pong tile: 64)
       if (tn_pp) {
         // one workgroup per CU: as many K chunks as fill ONE round of 256 workgroups when that occupies >= 85 % of them (h = 768: a
@@ -718,10 +663,7 @@ struct Batch {
         const int tiles = L.nprob * L.m_tiles * L.n_tiles;
         const int ks1 = 256 / tiles > 0 ? 256 / tiles : 1, ks2 = 512 / tiles > 0 ? 512 / tiles : 1;
         const double e1 = tiles * ks1 / 256.0, e2 = tiles * ks2 / 512.0;
-        static int force = -1;
-        if (force < 0) force = measure_env("GH_TN_PP_KS", 0);
         ks = (e1 >= 0.85 || e1 >= e2) ? ks1 : ks2;
-        if (force > 0) ks = force;
         const int kmax = k_total / 1024 > 1 ? k_total / 1024 : 1;
         if (ks > kmax) ks = kmax;
         // (the partial tiles must fit the workspace: fewer chunks otherwise)
@@ -729,13 +671,13 @@ struct Batch {
         for (int i = 0; i < L.nprob; ++i) out_bytes += ((size_t)L.p[i].M * L.p[i].N + (cs_out[i] ? (size_t)L.p[i].M : 0)) * sizeof(float);
         while (ks > 1 && (size_t)ks * out_bytes > g_ws_bytes) --ks;
       } else
-      if (xcd_rule && ks >= 12) ks = ((ks + 4) / 8) * 8;
+      if (ks >= 12) ks = ((ks + 4) / 8) * 8;
       int chunk = (k_total + ks - 1) / ks;
       chunk = ((chunk + align - 1) / align) * align;
       L.kchunk = chunk;
       L.ksplit = (k_total + chunk - 1) / chunk;
       if (tn_pp) L.per = (L.nprob * L.m_tiles * L.n_tiles * L.ksplit + 7) / 8;
-      if (!tn_pp && xcd_rule && L.ksplit >= 12 && L.ksplit % 8 != 0) {      // rounding the chunk up dropped a chunk or two: stretch the chunks to the multiple of 8 below
+      if (!tn_pp && L.ksplit >= 12 && L.ksplit % 8 != 0) {      // rounding the chunk up dropped a chunk or two: stretch the chunks to the multiple of 8 below
         const int k8 = (L.ksplit / 8) * 8;
         chunk = (((k_total + k8 - 1) / k8 + align - 1) / align) * align;
         if ((k_total + chunk - 1) / chunk % 8 == 0) { L.kchunk = chunk; L.ksplit = (k_total + chunk - 1) / chunk; }
@@ -814,19 +756,14 @@ struct Batch {
 
   hipError_t launch_any() {
     if (tn && tn_pp) return launch_tn_pp(L, s);
-#ifdef GH_MEASURE      // (the fp32 ping-pong tile is a measured-and-dropped experiment, DESIGN 4.5: instantiated in the tool build only)
-    if (pp32 && !tn && L.ksplit == 1 && !L.p[0].elt) return launch_cfg<4, 2, 5>(L, tn, s);
-#endif
     if (narrow && !tn && L.ksplit == 1 && !L.p[0].elt) return launch_cfg<2, 2, 5>(L, tn, s);
     if (big && !tn && L.ksplit == 1 && !L.p[0].elt) {
       // Occupancy-aware tile choice.  The chip holds 768 workgroups of either configuration (3 per CU); a grid of 64-row
       // tiles that ends in a thinly filled last round (e.g. 976 workgroups = 1.27 rounds, the node-compact single-problem
       // launches) runs faster on 32-row tiles (1937 workgroups = 2.52 rounds): measured 83 vs 78 TF at K = 300.
-      static int mode = -1;
-      if (mode < 0) mode = measure_env("GH_NT_TILE_RULE", 1);
       const double r = (double)L.m_tiles * L.nprob / 768.0;
       const double frac = r - (double)(long long)r;
-      if (mode == 1 && g_gemm_mode != 1 && r < 3.0 && frac > 0.02 && frac < 0.45) {
+      if (g_gemm_mode != 1 && r < 3.0 && frac > 0.02 && frac < 0.45) {
         int mt = 0;
         for (int i = 0; i < L.nprob; ++i) { const int t = (L.p[i].M + 31) / 32; if (t > mt) mt = t; }
         L.m_tiles = mt;
@@ -846,7 +783,6 @@ struct Batch {
       L.m_tiles = mt;
       return launch_cfg<2, 2, 8, 4>(L, tn, s);
     }
-    if (wide128) return launch_cfg<2, 2, 4, 4>(L, tn, s);
     if (wide) return launch_cfg<2, 2, 8, 4>(L, tn, s);
     return big ? launch_cfg<2, 2, 10>(L, tn, s) : launch_cfg<1, 4, 5>(L, tn, s);
   }
@@ -855,8 +791,7 @@ struct Batch {
   // workgroups, keep the partial tiles in the workspace and finish with nt_finish_kernel.
   bool nt_split_plan() {
     const int blocks = L.m_tiles * L.nprob;
-    static int max_blocks = -1;
-    if (max_blocks < 0) max_blocks = measure_env("GH_NT_SPLIT_BLOCKS", 96);
+    constexpr int max_blocks = 96;
     if (g_ws == nullptr || blocks >= max_blocks || !fast_ok(L, false)) return false;
     int tmax = 0;          // K tiles over the concatenated segments (every problem of a launch is split alike)
     for (int i = 0; i < L.nprob; ++i) {
@@ -871,9 +806,7 @@ struct Batch {
     // workgroups wanted: one per CU -- two for long contractions (>= 128 K tiles, e.g. the evidence-level attention at h = 768:
     // K = 6272), where a split-K workgroup is MFMA-bound rather than latency-bound (A/B configs[4] bf16: 256 / 512 / 768 =
     // 107.7 / 108.7 / 108.1 K pairs/s; headline and Snopes-count steps unchanged at any of them)
-    static int target = -1;
-    if (target < 0) target = measure_env("GH_NT_SPLIT_TARGET", 0);
-    const int tgt = target > 0 ? target : (tmax >= 128 ? 512 : 256);
+    const int tgt = tmax >= 128 ? 512 : 256;
     const int want = (tgt + blocks - 1) / blocks;
     if (ks > want) ks = want;
     if (ks < 2) return false;

@@ -207,7 +207,7 @@ gemm_tn_pp_kernel(const Launch L_byval) {
 #undef GH_TP_MCS
 #undef GH_TP_TILE
 
-  if (GH_DBG_BITS(L) & 1) {      // (tool build: K loop only)
+  if (GH_DBG_BITS(L) & DBG_NO_EPILOGUE) {      // (tool build: K loop only)
     float s = acs[0][0] + acs[1][0];
 #pragma unroll
     for (int mi = 0; mi < 8; ++mi)

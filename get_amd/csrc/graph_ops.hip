@@ -357,132 +357,6 @@ spmm_kernel(const uint64_t* __restrict__ bits, const float* __restrict__ dinv, c
   }
 }
 
-// LDS-free variant for float4-shaped rows: every thread owns output float4s (row i, column c) of one
-// graph and gathers its neighbours' float4s straight from L1/L2 (neighbours of node i are almost always
-// the adjacent nodes, so the gathers hit lines its wave neighbours just touched).  No staging phase and
-// no barrier: ~8 independent 16-byte loads in flight per thread, 8 waves per SIMD.
-__global__ void __launch_bounds__(256)
-spmm_gather_kernel(const uint64_t* __restrict__ bits, const float* __restrict__ dinv, const float* __restrict__ vals,
-                   const uint64_t* __restrict__ keep, const float* __restrict__ x, float* __restrict__ y, int R, int H,
-                   int transpose, int accumulate, int blocks_per_graph) {
-  const int g = blockIdx.x / blocks_per_graph, part = blockIdx.x % blocks_per_graph;
-  const int W = (R + 63) / 64, H4 = H / 4;
-  const float4* xg = reinterpret_cast<const float4*>(x + (size_t)g * R * H);
-  float4* yg = reinterpret_cast<float4*>(y + (size_t)g * R * H);
-  const uint64_t* bg = bits + (size_t)g * R * W;
-  const uint64_t* kg = keep ? keep + (size_t)g * W : nullptr;
-  const float* dg = dinv ? dinv + (size_t)g * R : nullptr;
-  const float* vg = vals ? vals + (size_t)g * R * R : nullptr;
-  const int total = R * H4;
-  for (int it = part * 256 + threadIdx.x; it < total; it += blocks_per_graph * 256) {
-    const int i = it / H4, c = it % H4;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float di = dg ? dg[i] : 0.f;
-    bool ki = true;
-    if (kg) ki = (kg[i >> 6] >> (i & 63)) & 1ull;
-    for (int w = 0; w < W; ++w) {
-      unsigned long long m = bg[(size_t)i * W + w];
-      if (kg && !ki) m &= kg[w];
-      // neighbours in batches of 8: collect the indices first (pure bit work), then issue all 16-byte
-      // gathers back to back so their latencies overlap instead of chaining
-      while (m) {
-        int nb[8];
-        int cnt = 0;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const bool on = m != 0ull;
-          nb[q] = on ? (w << 6) + __builtin_ctzll(m) : 0;
-          cnt += on;
-          m &= m - 1;                       // m == 0 stays 0
-        }
-        float4 xv[8];
-        float wt[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-          if (q < cnt) {
-            xv[q] = xg[(size_t)nb[q] * H4 + c];
-            wt[q] = vg ? (transpose ? vg[(size_t)nb[q] * R + i] : vg[(size_t)i * R + nb[q]]) : di * dg[nb[q]];
-          }
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-          if (q < cnt) {
-            acc.x += wt[q] * xv[q].x; acc.y += wt[q] * xv[q].y; acc.z += wt[q] * xv[q].z; acc.w += wt[q] * xv[q].w;
-          }
-      }
-    }
-    float4* o = yg + (size_t)i * H4 + c;
-    if (accumulate) { const float4 p = *o; acc.x += p.x; acc.y += p.y; acc.z += p.z; acc.w += p.w; }
-    *o = acc;
-  }
-}
-
-// Wave-per-row variant: the neighbour bit rows are wave-uniform (scalar registers, SALU bit walk), every
-// lane owns one or two float4 columns of the output row, neighbours are consumed four at a time so that
-// up to eight 16-byte gathers are in flight per lane with no divergence at all.
-template <int RPW>
-__global__ void __launch_bounds__(256)
-spmm_wave_kernel(const uint64_t* __restrict__ bits, const float* __restrict__ dinv, const float* __restrict__ vals,
-                 const uint64_t* __restrict__ keep, const float* __restrict__ x, float* __restrict__ y, int R, int H,
-                 int transpose, int accumulate, int waves_per_graph) {
-  const int lane = threadIdx.x & 63;
-  const int gw = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-  const int g = gw / waves_per_graph, r0 = (gw % waves_per_graph) * RPW;
-  const int W = (R + 63) / 64, H4 = H / 4;
-  const float4* xg = reinterpret_cast<const float4*>(x + (size_t)g * R * H);
-  float4* yg = reinterpret_cast<float4*>(y + (size_t)g * R * H);
-  const uint64_t* bg = bits + (size_t)g * R * W;
-  const uint64_t* kg = keep ? keep + (size_t)g * W : nullptr;
-  const float* dg = dinv ? dinv + (size_t)g * R : nullptr;
-  const float* vg = vals ? vals + (size_t)g * R * R : nullptr;
-  const bool two = lane + 64 < H4;
-  for (int i = r0; i < min(R, r0 + RPW); ++i) {
-    float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
-    const float di = dg ? dg[i] : 0.f;
-    bool ki = true;
-    if (kg) ki = (kg[i >> 6] >> (i & 63)) & 1ull;
-    for (int w = 0; w < W; ++w) {
-      unsigned long long m = bg[(size_t)i * W + w];
-      if (kg && !ki) m &= kg[w];
-      while (m) {
-        int nb[4];
-        int cnt = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const bool on = m != 0ull;
-          nb[q] = on ? (w << 6) + __builtin_ctzll(m) : 0;
-          cnt += on;
-          m &= m - 1;
-        }
-        float4 v0[4], v1[4];
-        float wt[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          if (q < cnt) {
-            if (lane < H4) v0[q] = xg[(size_t)nb[q] * H4 + lane];
-            if (two) v1[q] = xg[(size_t)nb[q] * H4 + lane + 64];
-            wt[q] = vg ? (transpose ? vg[(size_t)nb[q] * R + i] : vg[(size_t)i * R + nb[q]]) : di * dg[nb[q]];
-          }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          if (q < cnt) {
-            a0.x += wt[q] * v0[q].x; a0.y += wt[q] * v0[q].y; a0.z += wt[q] * v0[q].z; a0.w += wt[q] * v0[q].w;
-            a1.x += wt[q] * v1[q].x; a1.y += wt[q] * v1[q].y; a1.z += wt[q] * v1[q].z; a1.w += wt[q] * v1[q].w;
-          }
-      }
-    }
-    if (lane < H4) {
-      float4* o = yg + (size_t)i * H4 + lane;
-      if (accumulate) { const float4 p = *o; a0.x += p.x; a0.y += p.y; a0.z += p.z; a0.w += p.w; }
-      *o = a0;
-    }
-    if (two) {
-      float4* o = yg + (size_t)i * H4 + lane + 64;
-      if (accumulate) { const float4 p = *o; a1.x += p.x; a1.y += p.y; a1.z += p.z; a1.w += p.w; }
-      *o = a1;
-    }
-  }
-}
-
 // Edge-list variant of the slab kernel (the default for float4-shaped rows).  The bit-walk version above spends ~25
 // VALU instructions per (output float4, neighbour) -- 64-bit ctz / clear-lowest-bit / weight product per lane -- and was
 // VALU-issue-bound (1.4 G lane-instructions per launch at the bench shape = 35 us of a 47 us launch).  Here the
@@ -827,19 +701,18 @@ spmm_list_kernel(const uint64_t* __restrict__ bits, const float* __restrict__ di
 //   * Wave w owns the row tiles mi = w and w + 4 (R <= 128) and walks the slab's column tiles; only ceil(NR / 32) k-steps and
 //     ceil(NR / 16) row tiles are computed, so the work follows NR^2 in the node-compact layout.
 // Preconditions (launch_spmm): bf16 rows, R <= 128, h % 8 == 0, 16-byte aligned rows.
-// PIPE: slabs of 64 columns (128 B per row) in TWO 16 KB buffers -- the next slab's DMA is in flight under the current slab's MFMAs (same LDS
-// footprint as one 128-column slab; 32-byte units swizzled with ((r >> 1) & 1) | ((r >> 3) & 1) << 1: rows alternate between the two bank halves)
-template <int WAVES, bool PIPE>
-__global__ void __launch_bounds__(WAVES * 64, WAVES == 8 ? 1 : 2)
+// (round 6, measured equal and removed, DESIGN 4.5: eight waves with one row tile each; 64-column slabs in two buffers with the next
+//  slab's DMA under the current slab's MFMAs)
+__global__ void __launch_bounds__(256, 2)
 spmm_mfma_bf16_kernel(const uint64_t* __restrict__ bits, const float* __restrict__ dinv, const float* __restrict__ vals,
                       const uint64_t* __restrict__ keep, const int32_t* __restrict__ goff, const unsigned short* __restrict__ x,
                       unsigned short* __restrict__ y, int R, int H, int transpose, int accumulate, int n, int nslab, int seq) {
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
   typedef float f32x4_t __attribute__((ext_vector_type(4)));
-  constexpr int NT = 8 / WAVES, NTHR = WAVES * 64;      // row tiles per wave: wave w owns mi = w + WAVES t
-  constexpr int SC = PIPE ? 64 : 128, PITCH = SC * 2, CPR = PITCH / 16, BUFB = 128 * PITCH;      // slab columns, bytes per row, 16-byte chunks per row
-  __shared__ __attribute__((aligned(16))) unsigned char xs[128 * 256];      // [buffer][row][PITCH], rows 0 .. KR - 1 of a slab
+  constexpr int WAVES = 4, NT = 8 / WAVES, NTHR = WAVES * 64;      // row tiles per wave: wave w owns mi = w + WAVES t
+  constexpr int SC = 128, PITCH = SC * 2, CPR = PITCH / 16;      // slab columns, bytes per row, 16-byte chunks per row
+  __shared__ __attribute__((aligned(16))) unsigned char xs[128 * 256];      // [row][PITCH], rows 0 .. KR - 1 of a slab
   __shared__ float dv[128];
   constexpr unsigned OOB = 0x80000000u;
   int g, sl;
@@ -866,16 +739,16 @@ spmm_mfma_bf16_kernel(const uint64_t* __restrict__ bits, const float* __restrict
 
   // ---- the slab DMA (issued first: the operand build below runs under its flight)
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(x + (size_t)row0 * H), 0, 0x7fffffff, 0x00020000);
-  auto dma_slab = [&](int c0, int buf) __attribute__((always_inline)) {
+  auto dma_slab = [&](int c0) __attribute__((always_inline)) {
     const int chunks = KR * CPR;
     for (int base = 0; base < chunks; base += NTHR) {
       const int it = base + tid;                       // (chunks is a multiple of the workgroup size: no partial iteration)
       const int i = it / CPR, sl16 = it % CPR;
-      const int fz = PIPE ? ((((i >> 1) & 1) | (((i >> 3) & 1) << 1)) << 1) : (((i & 3) << 1) | (((i >> 3) & 1) << 3));
+      const int fz = ((i & 3) << 1) | (((i >> 3) & 1) << 3);
       const int c = sl16 ^ fz;
       const int col = c0 + 8 * c;
       const unsigned off = (i < NR && col < H) ? (unsigned)(i * H + col) * 2u : OOB;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)(xs + buf * BUFB + (base + wave * 64) * 16), 16, off, 0, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)(xs + (base + wave * 64) * 16), 16, off, 0, 0, 0);
     }
   };
   // Issue order = completion order on the vector-memory counter: the few small loads (bit rows, keep words, d^-1/2) go FIRST, the slab's
@@ -893,7 +766,7 @@ spmm_mfma_bf16_kernel(const uint64_t* __restrict__ bits, const float* __restrict
     }
   }
   __builtin_amdgcn_sched_barrier(0);
-  dma_slab(sl * SC, 0);
+  dma_slab(sl * SC);
   __builtin_amdgcn_sched_barrier(0);
 
   // ---- d^-1/2 of the graph's nodes (pattern mode) for everybody
@@ -946,7 +819,7 @@ spmm_mfma_bf16_kernel(const uint64_t* __restrict__ bits, const float* __restrict
 
   // ---- transpose-read base: lane (p = l15, g = q) points at row 8 q + (p >> 2) (+4: second read, +32 ks), four columns 4 (p & 3)
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)xs;
-  const int f5 = PIPE ? (((l15 >> 3) & 1) | ((q & 1) << 1)) : ((l15 >> 2) | ((q & 1) << 2));
+  const int f5 = (l15 >> 2) | ((q & 1) << 2);
   const unsigned rbase = lds0 + (unsigned)((8 * q + (l15 >> 2)) * PITCH + 8 * (l15 & 3));
   auto tr_read = [&](unsigned addr) __attribute__((always_inline)) {
     uint2 v;
@@ -957,33 +830,17 @@ spmm_mfma_bf16_kernel(const uint64_t* __restrict__ bits, const float* __restrict
   const int sl_end = min(nslab, sl + seq);
   for (int s_ = sl; s_ < sl_end; ++s_) {
     const int c0 = s_ * SC;
-    const unsigned bufo = PIPE ? (unsigned)(((s_ - sl) & 1) * BUFB) : 0u;
-    if constexpr (PIPE) {
-      // the other buffer was last read in the previous iteration, which ended with a barrier: restage it now.  The wait below lets
-      // exactly the next slab's DMA instructions of this wave (KR * CPR / NTHR = nks of them) stay in flight; everything older -- this
-      // slab's DMA and the previous slab's stores -- has then completed (vmcnt retires in order).
-      if (s_ + 1 < sl_end) {
-        dma_slab(c0 + SC, ((s_ - sl) & 1) ^ 1);
-        static_assert(!PIPE || WAVES == 4, "the counted wait below assumes nks DMA instructions per wave and slab");
-        if (nks == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-        else if (nks == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        else if (nks == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      asm volatile("s_barrier" ::: "memory");
-    } else {
-      if (s_ > sl) {
-        __syncthreads();                    // every wave is done with the previous slab's image
-        dma_slab(c0, 0);
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
+    if (s_ > sl) {
+      __syncthreads();                    // every wave is done with the previous slab's image
+      dma_slab(c0);
     }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
     const int ntile = (min(SC, H - c0) + 15) >> 4;
     // column tiles in pairs over two fragment sets: the next tile's transpose reads (and, accumulating, its y values) are in flight
     // while the current tile's MFMAs run
     auto load_b = [&](int ni, uint2* b0, uint2* b1) __attribute__((always_inline)) {
-      const unsigned ad = rbase + bufo + (unsigned)(((ni ^ f5) & (PIPE ? 3 : 7)) << 5);
+      const unsigned ad = rbase + (unsigned)(((ni ^ f5) & 7) << 5);
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks)
         if (ks < nks) { b0[ks] = tr_read(ad + ks * 32 * PITCH); b1[ks] = tr_read(ad + ks * 32 * PITCH + 4 * PITCH); }
@@ -1036,7 +893,7 @@ spmm_mfma_bf16_kernel(const uint64_t* __restrict__ bits, const float* __restrict
       }
     };
 #ifdef GH_MEASURE
-    if (accumulate & 512) { if constexpr (PIPE) asm volatile("s_barrier" ::: "memory"); continue; }      // tool build: set-up + slab DMA only
+    if (accumulate & 512) continue;      // tool build: set-up + slab DMA only
 #endif
     uint2 bA0[4], bA1[4], bB0[4], bB1[4];
     load_b(0, bA0, bA1);
@@ -1044,7 +901,6 @@ spmm_mfma_bf16_kernel(const uint64_t* __restrict__ bits, const float* __restrict
       tile(ni, bA0, bA1, bB0, bB1);
       if (ni + 1 < ntile) tile(ni + 1, bB0, bB1, bA0, bA1);
     }
-    if constexpr (PIPE) asm volatile("s_barrier" ::: "memory");      // (every transpose read of this buffer was waited for in tile())
   }
 #endif
 }
@@ -1070,11 +926,9 @@ int launch_spmm(const uint64_t* bits, const float* dinv, const float* vals, cons
   const int hv = h / V;
   // slab: <= 32 float4 (or 128 scalars) per row, as even as possible
   // (sized so that a workgroup's slab stays under ~32 KB of LDS: four to five workgroups per CU, also at R = 200)
-  static int cap_env = -2;
-  if (cap_env == -2) cap_env = measure_env("GH_SPMM_SLAB_KB", -1);
   // round 4, A/B on one box: many graphs of <= 128 nodes (the bench step's 960 x 100) run 0.4 % faster per STEP on 24 KB slabs (five
   // slabs of 15 float4 instead of four of 19), few graphs (218: the realistic step) 1 % slower
-  const int cap_kb = cap_env > 0 ? cap_env : ((goff && n >= 512 && r <= 128 && !bf16) ? 24 : 32);      // (node-compact layout only: the padded 100-row graphs run 58 -> 69 us on 24 KB slabs)   // measured per step: 48 KB -> 0.314 ms, 32 -> 0.288, 24 -> 0.294, 16 -> 0.344 (R = 100); R = 200: 0.60 -> 0.43
+  const int cap_kb = (goff && n >= 512 && r <= 128 && !bf16) ? 24 : 32;      // (node-compact layout only: the padded 100-row graphs run 58 -> 69 us on 24 KB slabs)   // measured per step: 48 KB -> 0.314 ms, 32 -> 0.288, 24 -> 0.294, 16 -> 0.344 (R = 100); R = 200: 0.60 -> 0.43
   const int lds_cap = (cap_kb * 1024) / (r * (v4 ? 16 : 4));
   const int slab_max = v4 ? (lds_cap < 32 ? (lds_cap < 4 ? 4 : lds_cap) : 32) : (lds_cap < 128 ? (lds_cap < 16 ? 16 : lds_cap) : 128);
   const int nslab = (hv + slab_max - 1) / slab_max;
@@ -1085,56 +939,33 @@ int launch_spmm(const uint64_t* bits, const float* dinv, const float* vals, cons
   const double rows = goff ? (double)m_real : (double)n * r;
   const double alg_bytes = (2.0 + (accumulate ? 1.0 : 0.0)) * rows * h * (bf16 ? 2.0 : 4.0) +
                            (double)n * ((double)r * W * 8.0 + (vals ? (double)r * r * 4.0 : (double)r * 4.0));
-  // 4 (default; 3 / 5: one / three columns per thread): edge-list slab kernel, LDS-DMA staging -- 62 us vs 69 us for the
-  // bit-walk slab kernel (0) on 960 x 100 x 300 Zipf word graphs, 50 vs 61 us on hub-free graphs;
-  // (a graph-per-workgroup pipeline over two LDS buffers, next slab's DMA in flight during the aggregation, measured
-  // slower -- 74-85 us at two workgroups per CU -- and was dropped);
-  // 1 / 2: LDS-free gather variants (thread-per-float4 / wave-per-row).  Measured equal or slower on MI355X: with
-  // ~8K waves in flight their sliding-window working set (~49 MB) thrashes the 32 MB of L2 (hit rate 32 %).
-  static int variant = -1;
-  if (variant < 0) { variant = measure_env("GH_SPMM_VARIANT", 4); if (variant > 5) variant = 4; }
-  // bf16 rows: columns per thread of the list kernel (tool build: GH_SPMM_BF16_CPT).  A bf16 column is an 8-byte LDS read and four
-  // unpack instructions in front of its FMAs, the per-edge overhead (list entry, address) weighs more than in fp32:
-  // 960 graphs x h = 768, window 5: 148.6 / 126.9 / 120.0 / 122.2 / 126.2 us at 1 / 2 / 3 / 4 / 6 columns per thread (fewer, longer work
-  // items per row beyond three: the last round of items is thinly filled)
-  static int bf_cpt = -1;
-  if (bf_cpt < 0) { bf_cpt = measure_env("GH_SPMM_BF16_CPT", 3); if (bf_cpt < 1 || bf_cpt > 3) bf_cpt = 3; }
   const int ptag = n < PROF_FEW_GROUPS ? PROF_FEW_ROWS : PROF_SPMM;
   prof_begin(s, ptag);
-  static int mfma_agg = -1;
-  if (mfma_agg < 0) mfma_agg = measure_env("GH_SPMM_MFMA", 1);
-  if (bf16 && mfma_agg && r <= 128 && h % 8 == 0 && variant >= 3) {
-    // bf16 rows: the aggregation as a dense product per graph on the matrix pipe (spmm_mfma_bf16_kernel)
-    static int mseq = -1, mw = -1, mpipe = -1;
-    if (mseq < 0) mseq = measure_env("GH_SPMM_MFMA_SEQ", 3);
-    if (mw < 0) mw = measure_env("GH_SPMM_MFMA_WAVES", 4);
-    if (mpipe < 0) mpipe = measure_env("GH_SPMM_MFMA_PIPE", 0);
-    const bool pipe = mpipe != 0 && mw != 8;
-    const int sc = pipe ? 64 : 128;
+  if (bf16 && r <= 128 && h % 8 == 0) {
+    // bf16 rows: the aggregation as a dense product per graph on the matrix pipe (spmm_mfma_bf16_kernel), slabs of 128 columns,
+    // three of them per workgroup (few-graph launches: one)
+    constexpr int sc = 128, mseq = 3;
     const int ns = (h + sc - 1) / sc;
-    int seq = n < 256 ? 1 : (pipe ? 2 * mseq : mseq);
+    int seq = n < 256 ? 1 : mseq;
     if (seq > ns) seq = ns;
-    if (seq < 1) seq = 1;
     const int nchunk = (ns + seq - 1) / seq;
     const unsigned short* x16 = reinterpret_cast<const unsigned short*>(x);
     unsigned short* y16 = reinterpret_cast<unsigned short*>(y);
     const dim3 mgrid(((n + 7) / 8) * 8 * nchunk);
 #ifdef GH_MEASURE
-    static int mdbg = -1;
-    if (mdbg < 0) mdbg = measure_env("GH_SPMM_MFMA_NOSTORE", 0);
+    static const int mdbg = measure_env("GH_SPMM_MFMA_NOSTORE", 0);
     if (mdbg) accumulate |= 256 * mdbg;
 #endif
-    // (measured equal and kept in the tool build only, DESIGN 4.5: eight waves per workgroup with one row tile each -- GH_SPMM_MFMA_WAVES=8 --
-    //  and 64-column slabs in two buffers with the next slab's DMA under the current slab's MFMAs -- GH_SPMM_MFMA_PIPE=1)
-#ifdef GH_MEASURE
-    if (mw == 8) hipLaunchKernelGGL((spmm_mfma_bf16_kernel<8, false>), mgrid, dim3(512), 0, s, bits, dinv, vals, keep, goff, x16, y16, r, h, transpose, accumulate, n, ns, seq);
-    else if (pipe) hipLaunchKernelGGL((spmm_mfma_bf16_kernel<4, true>), mgrid, dim3(256), 0, s, bits, dinv, vals, keep, goff, x16, y16, r, h, transpose, accumulate, n, ns, seq);
-    else
-#endif
-    hipLaunchKernelGGL((spmm_mfma_bf16_kernel<4, false>), mgrid, dim3(256), 0, s, bits, dinv, vals, keep, goff, x16, y16, r, h, transpose, accumulate, n, ns, seq);
-  } else
-  if (v4 && variant >= 3 && r <= 256 && (!bf16 || hv % 2 == 0)) {
-    // edge-list kernel; variant 3: one column per thread, 4 (default): two, 5: three.  LDS pitch = slab columns.
+    hipLaunchKernelGGL(spmm_mfma_bf16_kernel, mgrid, dim3(256), 0, s, bits, dinv, vals, keep, goff, x16, y16, r, h, transpose, accumulate, n, ns, seq);
+  } else if (v4 && r <= 256 && (!bf16 || hv % 2 == 0)) {
+    // edge-list slab kernel, LDS-DMA staging -- 62 us vs 69 us for the bit-walk slab kernel on 960 x 100 x 300 Zipf word graphs,
+    // 50 vs 61 us on hub-free graphs.  fp32 rows: two columns per thread.  bf16 rows: three -- a bf16 column is an 8-byte LDS read and
+    // four unpack instructions in front of its FMAs, the per-edge overhead (list entry, address) weighs more than in fp32: 960 graphs
+    // x h = 768, window 5: 148.6 / 126.9 / 120.0 / 122.2 / 126.2 us at 1 / 2 / 3 / 4 / 6 columns per thread (fewer, longer work items
+    // per row beyond three: the last round of items is thinly filled).  LDS pitch = slab columns.
+    // (removed, DESIGN 4.5: LDS-free gather variants -- thread-per-float4 / wave-per-row, measured equal or slower: with ~8K waves in
+    //  flight their sliding-window working set (~49 MB) thrashes the 32 MB of L2 -- and a graph-per-workgroup pipeline over two LDS
+    //  buffers, 74-85 us)
     const int cap = 10 * r;                        // edges per graph the list holds (a window-5 word graph has <= 9 R)
     int lslab = slab;
     dim3 lgrid = grid;
@@ -1152,14 +983,11 @@ int launch_spmm(const uint64_t* bits, const float* dinv, const float* vals, cons
     // 3 lines 0.607 ms; 64 columns = 51 KB of LDS per workgroup 0.91 ms).  Up to 40 KB of slab image per workgroup.
     {
       const int col_b = bf16 ? 8 : 16, per_line = 128 / col_b;            // float4 columns per 128-byte line
-      static int aligned = -1;
-      if (aligned < 0) aligned = measure_env("GH_SPMM_LINE_SLABS", 1);
-      if (aligned && cap_env <= 0 && ((size_t)h * (bf16 ? 2 : 4)) % 128 == 0 && hv % per_line == 0) {
+      constexpr int line_kb = 40;
+      if (((size_t)h * (bf16 ? 2 : 4)) % 128 == 0 && hv % per_line == 0) {
         int best = 0;
-        static int line_kb = -1;
-        if (line_kb < 0) line_kb = measure_env("GH_SPMM_LINE_KB", 40);
         for (int c = per_line; c <= hv && (size_t)r * c * col_b <= (size_t)line_kb * 1024; c += per_line) best = c;
-        if (best >= 2 * per_line || (line_kb != 40 && best >= per_line)) {
+        if (best >= 2 * per_line) {
           const int ns = (hv + best - 1) / best;
           int even = (((hv + ns - 1) / ns) + per_line - 1) / per_line * per_line;      // as even as whole lines allow
           lslab = even;
@@ -1168,25 +996,18 @@ int launch_spmm(const uint64_t* bits, const float* dinv, const float* vals, cons
       }
     }
     const size_t llds = (size_t)r * lslab * (bf16 ? 8 : 16) + (size_t)cap * 8 + (size_t)(r + 1) * 4 + (size_t)r * 4 + 4 + (size_t)r * 8;   // + item table
-    const void* fn;
-    const int lv = variant > 5 ? 5 : variant;
-    if (bf16) {
-      const int c = lv == 3 ? 1 : lv == 5 ? 3 : bf_cpt;
-      fn = c == 1 ? (const void*)spmm_list_kernel<true, 1> : c == 3 ? (const void*)spmm_list_kernel<true, 3> : (const void*)spmm_list_kernel<true, 2>;
-    }
-    else fn = lv == 3 ? (const void*)spmm_list_kernel<false, 1> : lv == 5 ? (const void*)spmm_list_kernel<false, 3> : (const void*)spmm_list_kernel<false, 2>;
-    static bool attrl[6] = {false, false, false, false, false, false};
-    const int ai = bf16 ? (3 + (lv == 3 ? 0 : lv == 5 ? 2 : bf_cpt - 1)) : (lv - 3);
-    if (!attrl[ai] && llds > 64 * 1024) { (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attrl[ai] = true; }
+    const void* fn = bf16 ? (const void*)spmm_list_kernel<true, 3> : (const void*)spmm_list_kernel<false, 2>;
+    static bool attr16 = false, attr32 = false;
+    bool& attr = bf16 ? attr16 : attr32;
+    if (!attr && llds > 64 * 1024) { (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
     // slabs per workgroup, measured inside the bench step (ms of aggregation per step at 1 / 2 / all slabs per workgroup):
     //   960 graphs, R = 100, h = 300 fp32 (4 slabs): 0.302 / 0.282 / 0.262;   640 graphs, R = 200 (8 slabs): 0.536 / 0.467 / 0.426;
     //   960 graphs, h = 768 bf16 image, window 5 (5 slabs): 0.634 / 0.620 / 0.698 -- long per-slab work: the whole graph in one
     //   workgroup leaves one thinly balanced round.  Few-graph launches (claim side) keep one slab per workgroup: latency.
-    static int split = -1, spw_env = -1;
-    if (split < 0) split = measure_env("GH_SPMM_SPLIT", 1) | (measure_env("GH_SPMM_DBG", 0) << 8);
-    if (spw_env < 0) spw_env = measure_env("GH_SPMM_SPW", 0);
+    // split = 1: hub rows may hand their edge groups to items of their own (tool build: GH_SPMM_DBG << 8 runs one half of the kernel)
+    static const int split = 1 | (measure_env("GH_SPMM_DBG", 0) << 8);
     int ns_arg = (int)lgrid.y;
-    int seq = spw_env > 0 ? spw_env : (n < 256 ? 1 : (bf16 ? 2 : ns_arg));
+    int seq = n < 256 ? 1 : (bf16 ? 2 : ns_arg);
     if (seq > ns_arg) seq = ns_arg;
     lgrid = dim3(((n + 7) / 8) * 8 * ((ns_arg + seq - 1) / seq), 1);
     ZeroFill zf = {nullptr, 0, nullptr, 0};
@@ -1202,15 +1023,6 @@ int launch_spmm(const uint64_t* bits, const float* dinv, const float* vals, cons
     static bool attrb = false;
     if (!attrb && lds > 64 * 1024) { (void)hipFuncSetAttribute((const void*)spmm_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attrb = true; }
     hipLaunchKernelGGL((spmm_kernel<4, true>), grid, dim3(256), lds, s, bits, dinv, vals, keep, goff, x, y, r, h, slab, transpose, accumulate);
-  } else if (v4 && variant == 2 && h / 4 <= 128 && !goff) {
-    constexpr int RPW = 5;
-    const int wpg = (r + RPW - 1) / RPW;
-    hipLaunchKernelGGL(spmm_wave_kernel<RPW>, dim3((n * wpg + 3) / 4), dim3(256), 0, s, bits, dinv, vals, keep, x, y, r, h,
-                       transpose, accumulate, wpg);
-  } else if (v4 && variant == 1 && !goff) {
-    const int bpg = (r * (h / 4) + 2047) / 2048;      // ~8 float4 outputs per thread
-    hipLaunchKernelGGL(spmm_gather_kernel, dim3(n * bpg), dim3(256), 0, s, bits, dinv, vals, keep, x, y, r, h, transpose,
-                       accumulate, bpg);
   } else if (v4) {
     static bool attr4 = false;     // only raise the dynamic-LDS cap when a launch actually needs more than 64 KB
     if (!attr4 && lds > 64 * 1024) { (void)hipFuncSetAttribute((const void*)spmm_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr4 = true; }

@@ -1002,10 +1002,7 @@ __global__ void att_dpre_kernel(const float* __restrict__ de, const float* __res
   const bool act = rl < RL && cl < sw;
   // RB rows per thread and trip with all loads ahead of the math; the first trip's rows are requested before `de` is
   // staged (loads unconditional from clamped rows / columns; clamped duplicates are never consumed)
-#ifndef GH_DPRE_RB
-#define GH_DPRE_RB 4
-#endif
-  constexpr int RB = GH_DPRE_RB;
+  constexpr int RB = 4;
   const int c4c = min(c4, n4 - 1);
   const float4* tb = reinterpret_cast<const float4*>(t + (size_t)row0 * Ha) + c4c;
   float4 nxt[RB];
@@ -1116,11 +1113,9 @@ int launch_att_dpre(const float* de, const float* w2, const float* t, const int3
   // (evidence level) keep one slab per 64 columns
   // whole rows per workgroup up to 512 floats: a column slab makes every row a short run (400 B at three slabs) that
   // straddles 128-byte lines shared with the neighbouring slab's workgroup -- measured 3.1 / 3.6 / 3.9 / 4.3 TB/s at
-  // 5 / 3 / 2 / 1 slabs (GH_DPRE_SLABS) once the row batches are prefetched
-  static int nsl_env = -1;
-  if (nsl_env < 0) nsl_env = measure_env("GH_DPRE_SLABS", 0);
+  // 5 / 3 / 2 / 1 slabs once the row batches are prefetched
   // (round 5: 3 / 5 / 8 slabs for the few-pair launches -- evidence level, 32 workgroups of 30 rows -- measured: no effect on the step)
-  const int nsl = nsl_env > 0 ? nsl_env : (n4 + 127) / 128;
+  const int nsl = (n4 + 127) / 128;
   const int S4 = (n4 + nsl - 1) / nsl;
   const int RL = (256 / S4) > 0 ? (256 / S4) : 1;
   const int threads = ((S4 * RL + 63) / 64) * 64;

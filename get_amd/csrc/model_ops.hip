@@ -79,13 +79,11 @@ static int make_dims(const gh_get_model* Mo, const gh_get_batch* Ba, Dims& d) {
                  "get: storage = 1 needs the bf16 twins of both evidence cells' weights (gh_weights_refresh)");
     GH_REQUIRE(Mo->embedding16, "get: storage = 1 needs the bf16 copy of the word table (embedding16)");
   }
-  static int att16_on = -1;
-  if (att16_on < 0) att16_on = measure_env("GH_ATT16", 1);
   // att16 = "no fp32 copy of the second cell's output exists": it must imply every condition of att_fwd_impl's / att_bwd_impl's own
   // use16 predicate (gemm_ops.hip: bf16 gemm mode, >= 8192 rows, right / left / hidden widths multiples of 8) -- restated here in
   // full rather than relied upon by construction (d.bf already holds Mr >= 8192 and H % 8 == 0; the word attention's right and
   // left widths and its hidden width are all H)
-  d.att16 = d.bf && gemm_mode() == 1 && Mo->att_word_w1_16 && Mo->att_word_w1t_16 && att16_on && d.Mr >= 8192 && d.H % 8 == 0;
+  d.att16 = d.bf && gemm_mode() == 1 && Mo->att_word_w1_16 && Mo->att_word_w1t_16 && d.Mr >= 8192 && d.H % 8 == 0;
   return 0;
 }
 
@@ -536,9 +534,7 @@ extern "C" int gh_get_backward(const gh_get_model* Mo, const gh_get_batch* Ba, c
   const float* table1 = d.bf ? (const float*)Mo->embedding16 : Mo->embedding;
   if (phase != 2) {
     // ---- head
-    static int head_fused = -1;
-    if (head_fused < 0) head_fused = measure_env("GH_HEAD_BWD", 1);
-    if (head_fused && d.C <= 8 && H % 4 == 0 && Mo->out0_w && Mo->out1_w && head_bwd_lds(d.B, H, d.C, d.E, Mo->out0_w) > 0) {
+    if (d.C <= 8 && H % 4 == 0 && Mo->out0_w && Mo->out1_w && head_bwd_lds(d.B, H, d.C, d.E, Mo->out0_w) > 0) {
       // both layers' input gradients and the second layer's weight gradients in one launch (head_bwd_kernel)
       GH_TRY(launch_head_bwd(g_phi, A + f.y0, Mo->out1_w, Mo->out0_w, d.B, H, d.C, d.Xl, d.E, Wb + w.d_y0, Mo->d_out1_w, Mo->d_out1_b,
                              Wb + w.d_new_left, 0, Wb + w.d_att_e, s));
