@@ -44,6 +44,11 @@ SIGNATURES = {
     "gh_linear_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
     "gh_linear_bwd": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "gh_linear_wgrad_bf16": [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _P],
+    "gh_gat_layer_fwd": [_P] * 6 + [_I] * 5 + [_F, _I, _I, _F, _U] + [_P] * 5 + [_P],
+    "gh_gat_layer_bwd": [_P] * 6 + [_I] * 5 + [_F, _I, _I, _F, _U] + [_P] * 11 + [_P],
+    "gh_gcn_norm": [_P, _P, _P, _P, _I, _I, _P, _P],
+    "gh_feat_dropout": [_P, _P, _I, _I, _F, _U, _P],
+    "gh_scale_rows": [_P, _P, _P, _P, _I, _I, _P],
     "gh_evd_assemble_fwd": [_P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "gh_evd_assemble_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "gh_clamp_events": [_P, _I],

@@ -413,8 +413,9 @@ spmm_list_kernel(const uint64_t* __restrict__ bits, const float* __restrict__ di
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int c0 = sl * slab;
   // exact n / d for n, d < 2^16 by one multiply-high (a runtime integer division costs ~20 VALU instructions)
+  // (d = 1 has no 32-bit magic: magic_of wraps to 0, and fdiv returns n itself -- rows of one or two float4 columns, h = 4, 8)
   auto magic_of = [](int d) { return (unsigned)(0xFFFFFFFFu / (unsigned)d) + 1u; };
-  auto fdiv = [](int n, unsigned magic) { return (int)__umulhi((unsigned)n, magic); };
+  auto fdiv = [](int n, unsigned magic) { return magic ? (int)__umulhi((unsigned)n, magic) : n; };
   const int H4 = H / 4;
   int ncol = min(slab, H4 - c0);
   const int row0 = goff ? goff[g] : g * R;

@@ -4,7 +4,8 @@ Same class names, constructor arguments, ``forward()`` signatures, parameter nam
 as upstream, so ``MasterFC/master_get.py`` and reference checkpoints
 load unchanged:
 
-  Models/BiDAF/wrapper.py                      Linear, GGNN, GSL, GGNN_with_GSL, LSTM
+  Models/BiDAF/wrapper.py                      Linear, GGNN, GSL, GGNN_with_GSL, LSTM,
+                                               GraphAttentionLayer, GAT, GCN
   thirdparty/two_branches_attention.py         ConcatNotEqualSelfAtt, ConcatSelfAtt
   thirdparty/self_attention.py                 MultiHeadSelfAttentionICLR2017Extend
   Models/FCWithEvidences/graph_based_semantic_structure.py   Graph_basedSemantiStructure
@@ -232,6 +233,120 @@ class LSTM(nn.Module):
 
     def forward(self, *a, **k):
         raise RuntimeError("get_amd: the LSTM encoders are dead code in GET and are not part of the HIP hot path")
+
+
+# ------------------------------------------------------------------ Models/BiDAF/wrapper.py:7-67
+class GraphAttentionLayer(nn.Module):
+    """One GAT head: h = input W, masked (adj > 0) LeakyReLU edge softmax, attention dropout, att @ h, elu if concat.
+    A row without an edge attends uniformly to all L nodes (the reference's -9e15 fill).  W is (in, out), a (2 out, 1)."""
+
+    def __init__(self, in_features, out_features, dropout, alpha, concat=True):
+        super().__init__()
+        _drop_caches_on_load(self)
+        self.dropout = dropout
+        self.in_features = in_features
+        self.out_features = out_features
+        self.alpha = alpha
+        self.concat = concat
+        self.W = nn.Parameter(torch.zeros(size=(in_features, out_features)))
+        nn.init.xavier_uniform_(self.W.data, gain=1.414)
+        self.a = nn.Parameter(torch.zeros(size=(2 * out_features, 1)))
+        nn.init.xavier_uniform_(self.a.data, gain=1.414)
+        self.leakyrelu = nn.LeakyReLU(self.alpha)
+        self.last_seed = None       # attention-dropout seed of the last training-mode forward (ops.gat_dropout_mask)
+
+    def forward(self, input, adj):
+        """input (B,L,in); adj dense (B,L,L) or PackedAdj.  Returns (B,L,out)."""
+        adj = ops.gat_pattern(adj)
+        p, seed = _encoder_drop(self.training, self.dropout)
+        self.last_seed = seed if p > 0 else None
+        mode = ops.GAT_ELU if self.concat else ops.GAT_PLAIN
+        return ops.gat_layer(input, adj, [self], mode, 0, p, seed)
+
+    def __repr__(self):
+        return self.__class__.__name__ + " (" + str(self.in_features) + " -> " + str(self.out_features) + ")"
+
+
+def _encoder_drop(training: bool, p: float):
+    """(p, seed) of a training-mode dropout of the encoders, (0.0, 0) otherwise."""
+    if training and p > 0:
+        return float(p), ops.new_dropout_seed()
+    return 0.0, 0
+
+
+# ------------------------------------------------------------------ Models/BiDAF/wrapper.py:70-112
+class GAT(nn.Module):
+    """Dense GAT of the reference on the packed adjacency: every layer's heads in one projection GEMM and one
+    aggregation launch (ops.gat_layer).  Output: relu(sum of the output heads / L), L = x.size(1)."""
+
+    def __init__(self, input_size, hidden_size, output_size, head_num=3, num_layers=1, dropout=0.6, alpha=0.2):
+        super().__init__()
+        _drop_caches_on_load(self)
+        self.dropout = dropout
+        self.attentions = []
+        for _ in range(num_layers - 1):
+            self.attentions.append([GraphAttentionLayer(input_size, hidden_size, dropout=dropout, alpha=alpha, concat=True)
+                                    for _ in range(head_num)])
+            input_size = hidden_size * head_num
+        for i, layer in enumerate(self.attentions):
+            for j, attention in enumerate(layer):
+                self.add_module("layer_{}_{}".format(i, j), attention)
+        self.out_att = nn.ModuleList([GraphAttentionLayer(input_size, output_size, dropout=dropout, alpha=alpha, concat=False)
+                                      for _ in range(head_num)])
+        # training mode: the seeds of the last forward, in order (input dropout, then per layer: attention dropout,
+        # and the dropout in front of the output layer) -- ops.feat_dropout / ops.gat_dropout_mask replay them
+        self.last_seeds = None
+
+    def forward(self, x, adj):
+        """x (B,L,input_size); adj dense (B,L,L) or PackedAdj.  Returns (B,L,output_size)."""
+        adj = ops.gat_pattern(adj)
+        assert x.size(1) == adj.r, "GAT: x.size(1) must be the adjacency's node count"
+        seeds = []
+
+        def drop():
+            p, seed = _encoder_drop(self.training, self.dropout)
+            seeds.append(seed)
+            return p, seed
+
+        x = ops.feat_dropout(x, *drop())
+        for li, heads in enumerate(self.attentions):
+            x = ops.gat_layer(x, adj, heads, ops.GAT_ELU, li, *drop())
+        x = ops.feat_dropout(x, *drop())
+        x = ops.gat_layer(x, adj, list(self.out_att), ops.GAT_OUTPUT, len(self.attentions), *drop())
+        self.last_seeds = seeds if self.training and self.dropout > 0 else None
+        return x
+
+
+# ------------------------------------------------------------------ Models/BiDAF/wrapper.py:115-151
+class GCN(nn.Module):
+    """x = relu(linear(A_hat @ x)) per layer, A_hat = D^-1/2 A D^-1/2 with D the row sums of the adjacency values --
+    applied as bit rows + per-row scales (ops.GCNAdj), never as a dense matrix."""
+
+    def __init__(self, input_dim, hidden_dim, output_dim, num_layers=1, dropout=0.5):
+        super().__init__()
+        _drop_caches_on_load(self)
+        self.dropout = dropout
+        self.num_layers = num_layers
+        self.input_dim = input_dim
+        self.output_dim = output_dim
+        linears = []
+        for num in range(self.num_layers):
+            # the reference's quirk, kept: the LAST layer maps to hidden_dim, the others to output_dim
+            linears.append(Linear(input_dim, hidden_dim if num == num_layers - 1 else output_dim))
+            input_dim = hidden_dim
+        self.Linear = nn.ModuleList(linears)
+        self.last_seed = None       # input-dropout seed of the last training-mode forward (ops.feat_dropout)
+
+    def forward(self, x, adj):
+        """x (B,L,input_dim); adj dense (B,L,L) (weighted: its values are normalised) or PackedAdj."""
+        adj = ops.as_packed(adj)
+        p, seed = _encoder_drop(self.training, self.dropout)
+        self.last_seed = seed if p > 0 else None
+        x = ops.feat_dropout(x, p, seed)
+        a_hat = ops.GCNAdj(adj)
+        for linear in self.Linear:
+            x = ops.relu(linear(a_hat.apply(x)))
+        return x
 
 
 # ------------------------------------------------------------------ thirdparty/two_branches_attention.py:112-148

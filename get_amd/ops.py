@@ -805,6 +805,192 @@ def linear_wgrad_bf16(g16: torch.Tensor, x16: torch.Tensor, dw: torch.Tensor, db
     return dw
 
 
+# --------------------------------------------------------------------------- graph encoders (wrapper.py:7-151 GAT, GCN)
+class _FeatDropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, p, seed):
+        x = _f32(x)
+        y = torch.empty_like(x)
+        cols = x.shape[-1]
+        call("gh_feat_dropout", ptr(x), ptr(y), x.numel() // cols, cols, float(p), int(seed), stream())
+        ctx.p, ctx.seed = p, seed
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        g = _f32(g)
+        dx = torch.empty_like(g)
+        cols = g.shape[-1]
+        call("gh_feat_dropout", ptr(g), ptr(dx), g.numel() // cols, cols, float(ctx.p), int(ctx.seed), stream())
+        return dx, None, None
+
+
+def feat_dropout(x, p: float, seed: int):
+    """F.dropout(x, p) with the stateless mask: element (row, col) of x viewed as (numel/cols, cols) is kept iff
+    dropout_mask_reference(seed, numel/cols, cols, p)[row, col]."""
+    if p <= 0:
+        return x
+    return _FeatDropout.apply(x, p, seed)
+
+
+def gat_dropout_mask(seed: int, layer: int, heads: int, n: int, r: int, p: float):
+    """Host replica (tests) of gh_gat_layer_fwd's attention dropout: bool (heads, n, r, r), True = kept."""
+    m = dropout_mask_reference(seed, (layer + 1) * heads * n * r, r, p)
+    return m[layer * heads * n * r:].reshape(heads, n, r, r)
+
+
+def _gat_operands(heads):
+    """(W_cat^T [H*f][din], W_cat [din][H*f], a [H][2f]) of a list of GraphAttentionLayer-like modules (.W [din][f],
+    .a [2f][1]), cached like the transposes: recomputed only when a weight is replaced, written in place or the weight
+    epoch moves on."""
+    ws = tuple(m.W for m in heads)
+    as_ = tuple(m.a for m in heads)
+
+    def make_lin():
+        if _lib.gemm_mode() == "fp32x3p":
+            call("gh_weights_changed")
+        return torch.cat([_f32(w.detach()).t() for w in ws], 0).contiguous()
+
+    w_lin = derived("gat_w_lin", ws, make_lin)
+    w_cat = derived("gat_w_cat", ws, lambda: torch.cat([_f32(w.detach()) for w in ws], 1).contiguous())
+    a_cat = derived("gat_a", as_, lambda: torch.cat([_f32(a.detach()).reshape(1, -1) for a in as_], 0).contiguous())
+    return w_lin, w_cat, a_cat
+
+
+GAT_OUTPUT, GAT_ELU, GAT_PLAIN = 0, 1, 2      # gh_gat_layer_fwd modes
+
+
+class _GATLayer(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, adj: PackedAdj, cfg, w_lin, w_cat, a_cat, *params):
+        heads, f, alpha, mode, layer, drop_p, seed = cfg
+        n, r = adj.n, adj.r
+        x2 = _f32(x).reshape(-1, x.shape[-1])
+        assert x2.shape[0] == n * r, f"GAT input has {x2.shape[0]} rows, the adjacency {n} x {r} nodes"
+        din, F = x2.shape[1], heads * f
+        dev = x.device
+        e = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)
+        h, s, stats, hp = e(n * r, F), e(n * r, heads, 2), e(n * r, heads, 2), e(n * r, F)
+        out = e(n * r, f) if mode == GAT_OUTPUT else e(n * r, F)
+        call("gh_gat_layer_fwd", ptr(adj.bits), ptr(adj.vals), ptr(adj.keep), ptr(x2), ptr(w_lin), ptr(a_cat), n, r, din,
+             heads, f, float(alpha), mode, layer, float(drop_p), int(seed), ptr(h), ptr(s), ptr(stats), ptr(hp), ptr(out),
+             stream())
+        ctx.save_for_backward(x2, h, s, stats, hp, out)
+        ctx.adj, ctx.cfg, ctx.w_cat, ctx.a_cat, ctx.xshape = adj, cfg, w_cat, a_cat, x.shape
+        return out.view(*x.shape[:-1], out.shape[-1])
+
+    @staticmethod
+    def backward(ctx, g):
+        x2, h, s, stats, hp, out = ctx.saved_tensors
+        heads, f, alpha, mode, layer, drop_p, seed = ctx.cfg
+        adj = ctx.adj
+        n, r = adj.n, adj.r
+        din, F = x2.shape[1], heads * f
+        g2 = _f32(g).reshape(out.shape)
+        dev = g.device
+        _lib.ensure_workspace(dev)
+        dh = torch.empty_like(h)
+        da_part = torch.empty((n, heads, 2 * f), device=dev, dtype=torch.float32)
+        dx = torch.empty_like(x2) if ctx.needs_input_grad[0] else None
+        dw = torch.zeros((din, F), device=dev, dtype=torch.float32)
+        da = torch.zeros((heads, 2 * f), device=dev, dtype=torch.float32)
+        call("gh_gat_layer_bwd", ptr(adj.bits), ptr(adj.vals), ptr(adj.keep), ptr(x2), ptr(ctx.w_cat), ptr(ctx.a_cat), n, r,
+             din, heads, f, float(alpha), mode, layer, float(drop_p), int(seed), ptr(h), ptr(s), ptr(stats), ptr(hp),
+             ptr(out), ptr(g2), ptr(dh), ptr(da_part), ptr(dx), ptr(dw), ptr(da), stream())
+        dws = [dw[:, k * f:(k + 1) * f].contiguous() for k in range(heads)]
+        das = [da[k].reshape(2 * f, 1) for k in range(heads)]
+        return (dx.view(ctx.xshape) if dx is not None else None, None, None, None, None, None, *dws, *das)
+
+
+def gat_layer(x, adj: PackedAdj, heads, mode: int, layer: int = 0, drop_p: float = 0.0, seed: int = 0):
+    """All heads of one GAT layer (GraphAttentionLayer-like modules sharing alpha and width) in one projection GEMM and
+    one aggregation launch.  x (N,R,din) -> (N,R,H*f) (modes GAT_ELU / GAT_PLAIN, heads concatenated) or (N,R,f)
+    (GAT_OUTPUT: relu(sum of the heads / R)).  drop_p/seed: the attention dropout (gat_dropout_mask replays it)."""
+    f = heads[0].W.shape[1]
+    alpha = float(heads[0].alpha)
+    assert all(m.W.shape == heads[0].W.shape and float(m.alpha) == alpha for m in heads)
+    w_lin, w_cat, a_cat = _gat_operands(heads)
+    cfg = (len(heads), f, alpha, int(mode), int(layer), float(drop_p), int(seed))
+    return _GATLayer.apply(x, adj, cfg, w_lin, w_cat, a_cat, *[m.W for m in heads], *[m.a for m in heads])
+
+
+def gat_pattern(adj) -> PackedAdj:
+    """GAT adjacency: a dense (N,R,R) tensor is packed with its values (the kernels keep the entries > 0, as the
+    reference's `adj > 0` does); a PackedAdj is used as it is (its refined bit pattern, values > 0 where it has values)."""
+    return as_packed(adj)
+
+
+def gcn_scale(adj: PackedAdj) -> torch.Tensor:
+    """Per-row scale of the GCN normalisation D^-1/2 A D^-1/2 (gh_gcn_norm), (N, R)."""
+    scale = torch.empty((adj.n, adj.r), device=adj.device, dtype=torch.float32)
+    call("gh_gcn_norm", ptr(adj.bits), ptr(adj.dinv) if adj.vals is None else None, ptr(adj.vals), ptr(adj.keep), adj.n,
+         adj.r, ptr(scale), stream())
+    return scale
+
+
+class _ScaleRows(torch.autograd.Function):
+    """y = x * scale[row] (scale carries no gradient); the backward is the same scaling."""
+
+    @staticmethod
+    def forward(ctx, x, scale):
+        x = _f32(x)
+        y = torch.empty_like(x)
+        call("gh_scale_rows", ptr(x), ptr(scale), None, ptr(y), scale.numel(), x.numel() // scale.numel(), stream())
+        ctx.scale = scale
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        g = _f32(g)
+        dx = torch.empty_like(g)
+        call("gh_scale_rows", ptr(g), ptr(ctx.scale), None, ptr(dx), ctx.scale.numel(), g.numel() // ctx.scale.numel(),
+             stream())
+        return dx, None
+
+
+class _Relu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        x = _f32(x)
+        y = torch.empty_like(x)
+        cols = x.shape[-1]
+        call("gh_scale_rows", ptr(x), None, ptr(x), ptr(y), x.numel() // cols, cols, stream())
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        (y,) = ctx.saved_tensors
+        g = _f32(g)
+        dx = torch.empty_like(g)
+        cols = g.shape[-1]
+        call("gh_scale_rows", ptr(g), None, ptr(y), ptr(dx), g.numel() // cols, cols, stream())
+        return dx
+
+
+def relu(x):
+    return _Relu.apply(x)
+
+
+class GCNAdj:
+    """A_hat = D^-1/2 A D^-1/2 of a packed adjacency, applied without forming it: the normalised graph's A_hat is again a
+    normalised graph (bits + per-row scale), a weighted one is scale . A . scale around the fp32 aggregation."""
+
+    __slots__ = ("adj", "scale")
+
+    def __init__(self, adj: PackedAdj):
+        self.scale = gcn_scale(adj)
+        if adj.vals is None:
+            adj = PackedAdj(adj.bits, self.scale, None, adj.keep, adj.n, adj.r)
+        self.adj = adj
+
+    def apply(self, x):
+        """A_hat @ x for x (N,R,D) (the backward uses A_hat^T through gh_spmm's transposed mode)."""
+        if self.adj.vals is None:
+            return spmm(self.adj, x)
+        return _ScaleRows.apply(spmm(self.adj, _ScaleRows.apply(x, self.scale)), self.scale)
+
+
 # --------------------------------------------------------------------------- ragged helpers
 class Segments:
     """Claim -> evidence-pair segmentation of one batch (prefix sums live on the device)."""

@@ -293,6 +293,48 @@ int gh_linear_bwd(const float* x, const float* wt, const float* w, const float* 
 int gh_linear_wgrad_bf16(const void* g16, int ldg, const void* x16, int ldx, int m, int n, int k,
                          float* dw, int lddw, float* db, gh_stream_t stream);
 
+/* ---- graph encoders: Models/BiDAF/wrapper.py:7-67 GraphAttentionLayer, :70-112 GAT, :115-151 GCN ----
+ * Padded layout only (no node-compact plan), r <= 256 nodes per graph, fp32.
+ *
+ * One GAT layer, all `heads` heads at once (wrapper.py:27-53 per head; :99-108 the stack):
+ *   h   [n*r][heads*f]  = x [n*r][din] W_cat, one GEMM; W_cat = [W_0 | W_1 | ...] (each head's W is [din][f]), handed over
+ *                         TRANSPOSED as w_lin [heads*f][din] (the nn.Linear layout gh_linear_fwd takes)
+ *   a   [heads][2f]      each head's attention vector (the reference's a[2f][1])
+ *   e_ij = LeakyReLU_alpha(h_i . a[:f] + h_j . a[f:]) on the edges, softmax over j; an edge is a refined bit (keep-set as
+ *   in gh_spmm) whose value is > 0 when vals != NULL (the reference masks with adj > 0); a row without an edge is uniform,
+ *   1/r over all r nodes (the reference's -9e15 fill).  drop_p > 0: dropout of the attention entries with the stateless
+ *   mask of the cells, entry (head hd, graph g, i, j) kept iff hash(drop_seed, (((layer*heads + hd)*n + g)*r + i)*r + j)
+ *   >= drop_p*2^32, scaled by 1/(1-drop_p).  hp [n*r][heads*f] = P h per head (saved).  mode 1 (hidden layer, concat=True):
+ *   out [n*r][heads*f] = elu(hp); mode 2 (a lone concat=False layer): out = hp; mode 0 (the GAT's output layer,
+ *   wrapper.py:108-110): out [n*r][f] = relu(sum_hd hp_hd / r).
+ *   Saved for the backward: s [n*r][heads][2] the score halves, stats [n*r][heads][2] = (row max, 1 / row sum).
+ *   Needs heads <= 8, f <= 1024. */
+int gh_gat_layer_fwd(const uint64_t* bits, const float* vals, const uint64_t* keep, const float* x, const float* w_lin,
+                     const float* a, int n, int r, int din, int heads, int f, float alpha, int mode, int layer,
+                     float drop_p, uint32_t drop_seed, float* h, float* s, float* stats, float* hp, float* out,
+                     gh_stream_t stream);
+/* Backward of the layer: same arguments as the forward, its saved tensors, and g = dL/dout ([n*r][heads*f] or [n*r][f]).
+ * w_cat [din][heads*f] (the W's side by side, as stored).  Scratch: dh [n*r][heads*f], da_part [n][heads][2f].
+ * Outputs: dx [n*r][din] (NULL ok), and ACCUMULATED (+=) into dw_cat [din][heads*f] and da [heads][2f].
+ * No global atomics: column sums of the edge softmax are reduced in LDS, da over the graphs in a fixed order. */
+int gh_gat_layer_bwd(const uint64_t* bits, const float* vals, const uint64_t* keep, const float* x, const float* w_cat,
+                     const float* a, int n, int r, int din, int heads, int f, float alpha, int mode, int layer,
+                     float drop_p, uint32_t drop_seed, const float* h, const float* s, const float* stats,
+                     const float* hp, const float* out, const float* g, float* dh, float* da_part, float* dx,
+                     float* dw_cat, float* da, gh_stream_t stream);
+/* GCN normalisation (wrapper.py:125-135): D^-1/2 A D^-1/2 with D the row sums of the adjacency VALUES over the refined
+ * pattern, pow(-0.5) with inf -> 0, written as a per-row scale [n][r]:
+ *   vals == NULL (normalised graph, value dinv_i dinv_j): scale_i = dinv_i (dinv_i sum_{j in N(i)} dinv_j)^-1/2, and
+ *                 A_hat is again a normalised graph: gh_spmm with dinv = scale;
+ *   vals != NULL: scale_i = (sum_j vals_ij)^-1/2 and A_hat x = scale . (gh_spmm on vals)(scale . x)  (gh_scale_rows). */
+int gh_gcn_norm(const uint64_t* bits, const float* dinv, const float* vals, const uint64_t* keep, int n, int r,
+                float* scale, gh_stream_t stream);
+/* Feature dropout of the encoders (wrapper.py:101,105,141): y = x * mask / (1 - p), the cells' stateless mask over the
+ * element index row*cols + col (in-place ok; the backward is the same call on the gradient). */
+int gh_feat_dropout(const float* x, float* y, int rows, int cols, float p, uint32_t seed, gh_stream_t stream);
+/* y[i][c] = x[i][c] * scale[i] (scale NULL: 1), zeroed where mask[i][c] <= 0 (mask NULL: none; mask == x is relu(x)). */
+int gh_scale_rows(const float* x, const float* scale, const float* mask, float* y, int rows, int cols, gh_stream_t stream);
+
 /* ---- a8  ragged helpers: Models/FCWithEvidences/basic_fc_model.py:80-121 ----
  * offsets[b+1] int32 prefix sum of evidence counts (device). */
 /* has[b] (NULL ok) = 1.0 for claims with at least one evidence: row 0 of pad_right(x) is x's first row of the claim times has. */
