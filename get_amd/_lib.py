@@ -49,6 +49,10 @@ SIGNATURES = {
     "gh_gcn_norm": [_P, _P, _P, _P, _I, _I, _P, _P],
     "gh_feat_dropout": [_P, _P, _I, _I, _F, _U, _P],
     "gh_scale_rows": [_P, _P, _P, _P, _I, _I, _P],
+    "gh_query_att_fwd": [_P, _P, _P, _I, _I, _I, _P, _P, _P],
+    "gh_query_att_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
+    "gh_tanh_att_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "gh_tanh_att_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "gh_evd_assemble_fwd": [_P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "gh_evd_assemble_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "gh_clamp_events": [_P, _I],

@@ -25,8 +25,11 @@ def install():
     # thirdparty.two_branches_attention is star-imported by the model module (:9), which is also
     # where that module gets `nn` and `np` from
     _module("thirdparty.two_branches_attention", ConcatNotEqualSelfAtt=M.ConcatNotEqualSelfAtt,
-            ConcatSelfAtt=M.ConcatSelfAtt, torch=torch, nn=nn, np=np)
-    _module("thirdparty.self_attention", MultiHeadSelfAttentionICLR2017Extend=M.MultiHeadSelfAttentionICLR2017Extend)
+            ConcatSelfAtt=M.ConcatSelfAtt, Dot=M.Dot, BiLinear=M.BiLinear, BiLinearTanh=M.BiLinearTanh,
+            torch=torch, nn=nn, np=np)
+    _module("thirdparty.self_attention", MultiHeadSelfAttentionICLR2017Extend=M.MultiHeadSelfAttentionICLR2017Extend,
+            SelfAttentionICLR2017=M.SelfAttentionICLR2017,
+            MultiHeadSelfAttentionICLR17OnWord=M.MultiHeadSelfAttentionICLR17OnWord, SelfAttentionType=M.SelfAttentionType)
     # the model itself (master_get.py:5,145)
     _module("Models.FCWithEvidences.graph_based_semantic_structure",
             Graph_basedSemantiStructure=M.Graph_basedSemantiStructure, KeyWordSettings=KeyWordSettings)

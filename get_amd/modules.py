@@ -6,8 +6,9 @@ load unchanged:
 
   Models/BiDAF/wrapper.py                      Linear, GGNN, GSL, GGNN_with_GSL, LSTM,
                                                GraphAttentionLayer, GAT, GCN
-  thirdparty/two_branches_attention.py         ConcatNotEqualSelfAtt, ConcatSelfAtt
-  thirdparty/self_attention.py                 MultiHeadSelfAttentionICLR2017Extend
+  thirdparty/two_branches_attention.py         ConcatNotEqualSelfAtt, ConcatSelfAtt, Dot, BiLinear, BiLinearTanh
+  thirdparty/self_attention.py                 MultiHeadSelfAttentionICLR2017Extend, SelfAttentionICLR2017,
+                                               MultiHeadSelfAttentionICLR17OnWord, SelfAttentionType
   Models/FCWithEvidences/graph_based_semantic_structure.py   Graph_basedSemantiStructure
 
 Adjacency arguments may be the reference's dense ``(N,R,R)`` tensors (any float dtype; packed once
@@ -16,6 +17,7 @@ on the device, values kept exactly) or a native :class:`get_amd.ops.PackedAdj` f
 """
 from __future__ import annotations
 
+from enum import IntEnum
 from typing import Tuple
 
 import numpy as np
@@ -385,6 +387,110 @@ class MultiHeadSelfAttentionICLR2017Extend(nn.Module):
         assert tsr.size(-1) == self.inp_dim
         attended, weights = ops.concat_att(None, tsr, mask, self.linear1.weight, self.linear2.weight)
         attended = attended.permute(0, 2, 1)       # (B, C, D)
+        if return_att_weights:
+            return attended, weights
+        return attended
+
+
+# ------------------------------------------------------------------ thirdparty/self_attention.py:8-10
+class SelfAttentionType(IntEnum):
+    MultiHeadAttentionTanh = 1
+    MultiHeadAttentionTransformer = 2
+
+
+def _query_att_checks(left: torch.Tensor, right: torch.Tensor):
+    assert left.size(0) == right.size(0) and left.size(-1) == right.size(-1), "Must same dimensions"
+    assert len(left.size()) == 2 and len(right.size()) == 3
+
+
+# ------------------------------------------------------------------ thirdparty/two_branches_attention.py:9-38
+class Dot(nn.Module):
+    """Attention of `left` (B,D) over `right` (B,L,D) by dot product; returns (avg (B,D), weights (B,L))."""
+
+    def forward(self, left: torch.Tensor, right: torch.Tensor, mask: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        _query_att_checks(left, right)
+        _lib.require_cuda(left, right, mask)
+        return ops.query_att(left, right, mask)
+
+
+# ------------------------------------------------------------------ thirdparty/two_branches_attention.py:41-70
+class BiLinear(nn.Module):
+    """Dot attention with the query W(left)."""
+
+    def __init__(self, dim: int):
+        super().__init__()
+        _drop_caches_on_load(self)
+        self.W = nn.Linear(dim, dim)
+
+    def forward(self, left: torch.Tensor, right: torch.Tensor, mask: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        _query_att_checks(left, right)
+        _lib.require_cuda(left, right, mask)
+        return ops.query_att(ops.linear(left, self.W.weight, self.W.bias), right, mask)
+
+
+# ------------------------------------------------------------------ thirdparty/two_branches_attention.py:151-191
+class BiLinearTanh(nn.Module):
+    """combine(tanh(left_linear(left_tsr) + right_linear(right_tsr))) scores the SEQUENCE `left_tsr` (B,L,H), the first
+    argument, against the query `right_tsr` (B,D); returns (attended (B,H), weights (B,L))."""
+
+    def __init__(self, left_dim: int, right_dim: int, out_dim: int):
+        super().__init__()
+        _drop_caches_on_load(self)
+        self.left_linear = nn.Linear(left_dim, out_dim, bias=True)
+        self.right_linear = nn.Linear(right_dim, out_dim, bias=False)
+        self.combine = nn.Linear(out_dim, 1, bias=False)
+
+    def forward(self, left_tsr: torch.Tensor, right_tsr: torch.Tensor, mask: torch.Tensor):
+        assert len(left_tsr.size()) == 3 and len(mask.size()) == 2
+        _lib.require_cuda(left_tsr, right_tsr, mask)
+        pre = ops.linear(left_tsr, self.left_linear.weight, self.left_linear.bias)
+        u = ops.linear(right_tsr, self.right_linear.weight)
+        attended, weights = ops.tanh_att(pre, u, self.combine.weight, mask, left_tsr)
+        return attended.squeeze(1), weights.squeeze(-1)
+
+
+# ------------------------------------------------------------------ thirdparty/self_attention.py:13-48
+class SelfAttentionICLR2017(nn.Module):
+    """Single-head structured self-attention; returns avg (B,D) only.  `num_heads` sizes linear2 as in the reference,
+    whose forward works for num_heads == 1 alone (its mask no longer broadcasts otherwise): other values raise here."""
+
+    def __init__(self, inp_dim: int, out_dim: int, num_heads: int = 1):
+        super().__init__()
+        self.inp_dim, self.out_dim = inp_dim, out_dim
+        _drop_caches_on_load(self)
+        self.linear1 = nn.Linear(inp_dim, out_dim, bias=False)
+        self.linear2 = nn.Linear(out_dim, num_heads, bias=False)
+
+    def forward(self, tsr: torch.Tensor, mask: torch.Tensor):
+        assert len(tsr.size()) == 3
+        assert tsr.size(-1) == self.inp_dim
+        num_heads = self.linear2.weight.shape[0]
+        if num_heads != 1:
+            raise RuntimeError(f"SelfAttentionICLR2017: num_heads={num_heads}, but the forward is defined for num_heads == 1 only "
+                               "(the reference's mask does not broadcast over several heads)")
+        _lib.require_cuda(tsr, mask)
+        pre = ops.linear(tsr, self.linear1.weight)
+        attended, _ = ops.tanh_att(pre, None, self.linear2.weight, mask, tsr)
+        return attended.squeeze(1)
+
+
+# ------------------------------------------------------------------ thirdparty/self_attention.py:103-153
+class MultiHeadSelfAttentionICLR17OnWord(nn.Module):
+    """Multi-head structured self-attention scored on `tsr` (B,L,D), averaging `original` (B,L,X); returns (B,C,X)."""
+
+    def __init__(self, inp_dim: int, out_dim: int, num_heads: int):
+        super().__init__()
+        self.inp_dim, self.out_dim, self.num_heads = inp_dim, out_dim, num_heads
+        _drop_caches_on_load(self)
+        self.linear1 = nn.Linear(inp_dim, out_dim, bias=False)
+        self.linear2 = nn.Linear(out_dim, num_heads, bias=False)
+
+    def forward(self, original: torch.Tensor, tsr: torch.Tensor, mask: torch.Tensor, return_att_weights=False):
+        assert len(tsr.size()) == 3
+        assert tsr.size(-1) == self.inp_dim
+        _lib.require_cuda(original, tsr, mask)
+        pre = ops.linear(tsr, self.linear1.weight)
+        attended, weights = ops.tanh_att(pre, None, self.linear2.weight, mask, original)
         if return_att_weights:
             return attended, weights
         return attended

@@ -741,6 +741,95 @@ def concat_att(left, right, mask, w1, w2, plan: "RaggedPlan" = None):
     return _ConcatAtt.apply(left, right, mask, w1, w2, plan)
 
 
+# --------------------------------------------------------------------------- single-query attention ablations
+def _mask_f32(mask: torch.Tensor) -> torch.Tensor:
+    """Masks of any dtype are compared with zero (the reference's `mask == 0`): 1.0 = real, 0.0 = padding."""
+    return (mask != 0).to(torch.float32).contiguous()
+
+
+class _QueryAtt(torch.autograd.Function):
+    """two_branches_attention.py:29-37 (Dot) / :62-69 (BiLinear, q = W(left)): csrc/attention_ops.hip gh_query_att_*."""
+
+    @staticmethod
+    def forward(ctx, q, right, mask):
+        _lib.require_cuda(q, right, mask)
+        q, right = _f32(q), _f32(right)
+        b, l, d = right.shape
+        assert q.shape == (b, d) and mask.shape == (b, l), "query_att: q (B,D), right (B,L,D), mask (B,L)"
+        weights = torch.empty((b, l), device=right.device, dtype=torch.float32)
+        avg = torch.empty((b, d), device=right.device, dtype=torch.float32)
+        call("gh_query_att_fwd", ptr(q), ptr(right), ptr(_mask_f32(mask)), b, l, d, ptr(weights), ptr(avg), stream())
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(q, right, weights)
+        return avg, weights
+
+    @staticmethod
+    def backward(ctx, g_avg, g_w):
+        q, right, weights = ctx.saved_tensors
+        b, l, d = right.shape
+        g_avg = _f32(g_avg) if g_avg is not None else torch.zeros_like(q)
+        g_w = _f32(g_w) if g_w is not None else None
+        dq = torch.empty_like(q)
+        dright = torch.empty_like(right)
+        call("gh_query_att_bwd", ptr(q), ptr(right), ptr(weights), ptr(g_avg), ptr(g_w), b, l, d, ptr(dq), ptr(dright), stream())
+        return dq, dright, None
+
+
+def query_att(q, right, mask):
+    """q (B,D), right (B,L,D), mask (B,L) -> avg (B,D), weights (B,L); both outputs are differentiable."""
+    return _QueryAtt.apply(q, right, mask)
+
+
+class _TanhAtt(torch.autograd.Function):
+    """two_branches_attention.py:183-190 (BiLinearTanh) / self_attention.py:39-47, :143-150: gh_tanh_att_*."""
+
+    @staticmethod
+    def forward(ctx, pre, u, w2, mask, values):
+        _lib.require_cuda(pre, u, w2, mask, values)
+        pre, values = _f32(pre), _f32(values)
+        b, l, ha = pre.shape
+        heads, dv = w2.shape[0], values.shape[2]
+        assert w2.shape[1] == ha and values.shape[:2] == (b, l) and mask.shape == (b, l), \
+            "tanh_att: pre (B,L,H), w2 (C,H), mask (B,L), values (B,L,X)"
+        if u is not None:
+            u = _f32(u)
+            assert u.shape == (b, ha), "tanh_att: u (B,H)"
+        w2c = _f32(w2.detach())
+        dev = pre.device
+        t = torch.empty((b, l, ha), device=dev, dtype=torch.float32)
+        weights = torch.empty((b, l, heads), device=dev, dtype=torch.float32)
+        attended = torch.empty((b, heads, dv), device=dev, dtype=torch.float32)
+        call("gh_tanh_att_fwd", ptr(pre), ptr(u), ptr(w2c), ptr(_mask_f32(mask)), ptr(values), b, l, ha, heads, dv, ptr(t),
+             ptr(weights), ptr(attended), stream())
+        ctx.set_materialize_grads(False)
+        ctx.has_u = u is not None
+        ctx.save_for_backward(t, w2c, weights, values)
+        return attended, weights
+
+    @staticmethod
+    def backward(ctx, g_att, g_w):
+        t, w2, weights, values = ctx.saved_tensors
+        b, l, ha = t.shape
+        heads, dv = w2.shape[0], values.shape[2]
+        dev = t.device
+        _lib.ensure_workspace(dev)      # the per-sequence dW2 partials
+        g_att = _f32(g_att) if g_att is not None else torch.zeros((b, heads, dv), device=dev)
+        g_w = _f32(g_w) if g_w is not None else None
+        dpre = torch.empty_like(t)
+        du = torch.empty((b, ha), device=dev, dtype=torch.float32) if ctx.has_u else None
+        dw2 = torch.zeros((heads, ha), device=dev, dtype=torch.float32)
+        dvalues = torch.empty_like(values)
+        call("gh_tanh_att_bwd", ptr(t), ptr(w2), ptr(weights), ptr(values), ptr(g_att), ptr(g_w), b, l, ha, heads, dv, ptr(dpre),
+             ptr(du), ptr(dw2), ptr(dvalues), stream())
+        return dpre, du, dw2, None, dvalues
+
+
+def tanh_att(pre, u, w2, mask, values):
+    """pre (B,L,H), u (B,H) or None, w2 (C,H), mask (B,L), values (B,L,X) -> attended (B,C,X), weights (B,L,C):
+    e = w2 tanh(pre + u), masked softmax over L per head, weighted sum of `values`.  Both outputs are differentiable."""
+    return _TanhAtt.apply(pre, u, w2, mask, values)
+
+
 # --------------------------------------------------------------------------- linear
 class _Linear(torch.autograd.Function):
     @staticmethod

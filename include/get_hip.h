@@ -335,6 +335,44 @@ int gh_feat_dropout(const float* x, float* y, int rows, int cols, float p, uint3
 /* y[i][c] = x[i][c] * scale[i] (scale NULL: 1), zeroed where mask[i][c] <= 0 (mask NULL: none; mask == x is relu(x)). */
 int gh_scale_rows(const float* x, const float* scale, const float* mask, float* y, int rows, int cols, gh_stream_t stream);
 
+/* ---- single-query attention ablations: thirdparty/two_branches_attention.py Dot :9-38, BiLinear :41-70, BiLinearTanh
+ *      :151-191; thirdparty/self_attention.py SelfAttentionICLR2017 :13-48, MultiHeadSelfAttentionICLR17OnWord :103-153 ----
+ * Padded layout only, fp32, mask [b][l] float (0 = padded), one workgroup per sequence, no floating-point atomics (two
+ * runs are bit-identical).  A sequence whose mask is all zero yields NaN weights and a NaN output row, as the reference's
+ * softmax of all -inf does; other sequences are unaffected.  Widths that are multiples of 4 on 16-byte aligned operands
+ * move 16 bytes per lane, every other shape takes a scalar path.
+ *
+ * Attention scored by a query vector (two_branches_attention.py:29-37 Dot; :62-69 BiLinear with q = W(left)):
+ *   s_l = right[b][l] . q[b];  weights[b] = softmax over the unmasked l (running maximum subtracted), exactly 0 where
+ *   masked;  avg[b] = sum_l weights[b][l] right[b][l].   Needs l <= 4096 and d <= 2048. */
+int gh_query_att_fwd(const float* q, const float* right, const float* mask, int b, int l, int d,
+                     float* weights /*[b][l]*/, float* avg /*[b][d]*/, gh_stream_t stream);
+/* Backward of the above from g_avg [b][d] and g_w [b][l] (NULL ok): with dw_l = g_w_l + g_avg . right_l and
+ * ds_l = w_l (dw_l - sum_j w_j dw_j):  dright_l = w_l g_avg + ds_l q,  dq = sum_l ds_l right_l.  Every row of dright is
+ * written (exact zeros where the weight is 0); nothing is accumulated. */
+int gh_query_att_bwd(const float* q, const float* right, const float* weights,
+                     const float* g_avg, const float* g_w /*NULL ok*/, int b, int l, int d,
+                     float* dq /*[b][d]*/, float* dright /*[b][l][d]*/, gh_stream_t stream);
+/* Additive (tanh) attention over a separate value tensor (two_branches_attention.py:183-190 BiLinearTanh with
+ * pre = left_linear(left_tsr), u = right_linear(right_tsr), w2 = combine.weight, values = left_tsr;
+ * self_attention.py:143-150 MultiHeadSelfAttentionICLR17OnWord and :39-47 SelfAttentionICLR2017 with pre = linear1(tsr),
+ * u = NULL, w2 = linear2.weight, values = original resp. tsr):
+ *   t = tanh(pre[b][l] + u[b]) (saved; rows of padded positions are not written),  e[b][l][c] = w2[c] . t,
+ *   weights = masked softmax over l per head,  attended[b][c] = sum_l weights[b][l][c] values[b][l].
+ * Needs heads <= 8 and l * heads <= 8192 (l <= 1024 at eight heads); longer sequences are rejected. */
+int gh_tanh_att_fwd(const float* pre /*[b][l][ha]*/, const float* u /*[b][ha] or NULL*/, const float* w2 /*[heads][ha]*/,
+                    const float* mask, const float* values /*[b][l][dv]*/, int b, int l, int ha, int heads, int dv,
+                    float* t /*saved tanh [b][l][ha]*/, float* weights /*[b][l][heads]*/, float* attended /*[b][heads][dv]*/,
+                    gh_stream_t stream);
+/* Backward from g_att [b][heads][dv] and g_w [b][l][heads] (NULL ok).  Out: dpre [b][l][ha] and dvalues [b][l][dv] (every
+ * row written, exact zeros at padded positions), du [b][ha] = sum_l dpre (NULL when the forward had no u); dw2 [heads][ha]
+ * is ACCUMULATED (+=) from per-sequence partials ([b][heads][ha] floats on the stream workspace, which must be registered:
+ * gh_set_stream_workspace / gh_set_workspace) summed over the sequences in a fixed order. */
+int gh_tanh_att_bwd(const float* t, const float* w2, const float* weights, const float* values,
+                    const float* g_att, const float* g_w /*NULL ok*/, int b, int l, int ha, int heads, int dv,
+                    float* dpre, float* du /*NULL when the forward had no u*/, float* dw2 /*ACCUMULATED*/, float* dvalues,
+                    gh_stream_t stream);
+
 /* ---- a8  ragged helpers: Models/FCWithEvidences/basic_fc_model.py:80-121 ----
  * offsets[b+1] int32 prefix sum of evidence counts (device). */
 /* has[b] (NULL ok) = 1.0 for claims with at least one evidence: row 0 of pad_right(x) is x's first row of the claim times has. */

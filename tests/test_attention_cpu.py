@@ -1,0 +1,102 @@
+"""CPU-side checks of the single-query attention ablations (thirdparty/two_branches_attention.py Dot, BiLinear,
+BiLinearTanh; thirdparty/self_attention.py SelfAttentionICLR2017, MultiHeadSelfAttentionICLR17OnWord, SelfAttentionType):
+the install() shim exports them under the reference's module paths, their constructors build the reference's state_dict
+for every configuration captured in tests/golden/attention_contract.json, and the golden archive is complete."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_install_shim_exports_the_attention_ablations(tmp_path):
+    os.makedirs(os.path.join(tmp_path, "thirdparty"), exist_ok=True)
+    open(os.path.join(tmp_path, "thirdparty", "__init__.py"), "w").close()
+    code = r"""
+import sys
+sys.path.insert(0, %r)
+sys.path.insert(0, %r)
+import get_amd
+M = get_amd.install()
+from thirdparty.two_branches_attention import Dot, BiLinear, BiLinearTanh, ConcatNotEqualSelfAtt, ConcatSelfAtt
+from thirdparty.self_attention import (SelfAttentionICLR2017, MultiHeadSelfAttentionICLR17OnWord, SelfAttentionType,
+                                       MultiHeadSelfAttentionICLR2017Extend)
+from get_amd import modules
+assert Dot is modules.Dot and BiLinear is modules.BiLinear and BiLinearTanh is modules.BiLinearTanh
+assert SelfAttentionICLR2017 is modules.SelfAttentionICLR2017
+assert MultiHeadSelfAttentionICLR17OnWord is modules.MultiHeadSelfAttentionICLR17OnWord
+assert ConcatNotEqualSelfAtt is modules.ConcatNotEqualSelfAtt and ConcatSelfAtt is modules.ConcatSelfAtt
+assert MultiHeadSelfAttentionICLR2017Extend is modules.MultiHeadSelfAttentionICLR2017Extend
+assert int(SelfAttentionType.MultiHeadAttentionTanh) == 1 and int(SelfAttentionType.MultiHeadAttentionTransformer) == 2
+assert [t.name for t in SelfAttentionType] == ['MultiHeadAttentionTanh', 'MultiHeadAttentionTransformer']
+print('ok')
+""" % (ROOT, str(tmp_path))
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stderr[-2000:]
+
+
+def test_attention_state_dicts_match_the_reference_contract(golden_dir):
+    from get_amd import modules
+    with open(os.path.join(golden_dir, "attention_contract.json")) as fh:
+        contract = json.load(fh)
+    assert {c["class"] for c in contract.values()} == {"Dot", "BiLinear", "BiLinearTanh", "SelfAttentionICLR2017",
+                                                       "MultiHeadSelfAttentionICLR17OnWord"}
+    for name, c in contract.items():
+        m = getattr(modules, c["class"])(**c["kwargs"])
+        got = [[k, list(v.shape)] for k, v in m.state_dict().items()]
+        assert got == c["state_dict"], name
+
+
+def test_self_attention_keeps_the_constructors_head_count():
+    from get_amd import modules
+    m = modules.SelfAttentionICLR2017(8, 7, num_heads=3)
+    assert m.linear2.weight.shape == (3, 7) and m.linear1.weight.shape == (7, 8) and m.linear1.bias is None
+    t = modules.BiLinearTanh(8, 5, 7)
+    assert t.left_linear.bias is not None and t.right_linear.bias is None and t.combine.weight.shape == (1, 7)
+
+
+def test_attention_modules_refuse_cpu_tensors():
+    from get_amd import modules
+    mask = torch.ones(2, 4)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        modules.Dot()(torch.zeros(2, 8), torch.zeros(2, 4, 8), mask)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        modules.BiLinear(8)(torch.zeros(2, 8), torch.zeros(2, 4, 8), mask)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        modules.BiLinearTanh(8, 5, 7)(torch.zeros(2, 4, 8), torch.zeros(2, 5), mask)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        modules.SelfAttentionICLR2017(8, 7)(torch.zeros(2, 4, 8), mask)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        modules.MultiHeadSelfAttentionICLR17OnWord(8, 7, 2)(torch.zeros(2, 4, 5), torch.zeros(2, 4, 8), mask)
+
+
+def test_attention_golden_archive_is_complete(golden_dir):
+    z = np.load(os.path.join(golden_dir, "g12_attention.npz"))
+    meta = json.loads(bytes(z["meta"]).decode())
+    assert set(meta["cases"]) == {"dot_d6", "dot_d8", "bilinear", "bilineartanh", "selfatt", "onword_h1", "onword_h3",
+                                  "dot_offset_pos", "dot_offset_neg"}
+    assert meta["geometries"] == {"b3l12": [3, 12], "b2l70": [2, 70]}
+    with open(os.path.join(golden_dir, "attention_contract.json")) as fh:
+        assert set(json.load(fh)) == set(meta["cases"])
+    for name in meta["cases"]:
+        for geom, (b, l) in meta["geometries"].items():
+            key = f"{name}/{geom}::"
+            have = {k[len(key):] for k in z.files if k.startswith(key)}
+            assert {"mask", "out", "gout"} <= have, key
+            assert z[key + "mask"].shape == (b, l)
+            if name != "selfatt":          # the only class that returns no weights
+                assert {"weights", "gweights"} <= have, key
+            # a gradient for every input and parameter
+            for k in have:
+                if k.startswith("param::"):
+                    assert "grad::" + k[len("param::"):] in have, key + k
+            inputs = have - {"mask", "out", "gout", "weights", "gweights"} - {k for k in have if "::" in k}
+            assert inputs and all("grad::" + k in have for k in inputs), (key, inputs)
+    for k in z.files:
+        if k != "meta":
+            assert np.isfinite(z[k]).all(), k
