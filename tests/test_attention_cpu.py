@@ -1,7 +1,8 @@
 """CPU-side checks of the single-query attention ablations (thirdparty/two_branches_attention.py Dot, BiLinear,
 BiLinearTanh; thirdparty/self_attention.py SelfAttentionICLR2017, MultiHeadSelfAttentionICLR17OnWord, SelfAttentionType):
 the install() shim exports them under the reference's module paths, their constructors build the reference's state_dict
-for every configuration captured in tests/golden/attention_contract.json, and the golden archive is complete."""
+for every configuration captured in tests/golden/attention_contract.json, the golden archive is complete, and the float64
+restatements the GPU tests compare the kernels with (tests/util.py) reproduce that archive on their own."""
 import json
 import os
 import subprocess
@@ -10,6 +11,8 @@ import sys
 import numpy as np
 import pytest
 import torch
+
+from tests.util import _module64, golden_ratio
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -100,3 +103,39 @@ def test_attention_golden_archive_is_complete(golden_dir):
     for k in z.files:
         if k != "meta":
             assert np.isfinite(z[k]).all(), k
+
+
+ARGS = {"Dot": ("left", "right"), "BiLinear": ("left", "right"), "BiLinearTanh": ("left_tsr", "right_tsr"),
+        "SelfAttentionICLR2017": ("tsr",), "MultiHeadSelfAttentionICLR17OnWord": ("original", "tsr")}
+
+
+def test_float64_restatements_reproduce_the_attention_goldens(golden_dir):
+    """_query64 / _tanh64 / _module64 alone, in float64 on the archive's inputs and parameters, against every captured
+    output, weight and gradient at the GPU golden test's elementwise bounds (1e-4 + 1e-4 |want| for outputs and weights,
+    1e-5 + 1e-4 |want| for gradients), the offset cases included."""
+    z = np.load(os.path.join(golden_dir, "g12_attention.npz"))
+    meta = json.loads(bytes(z["meta"]).decode())
+    with open(os.path.join(golden_dir, "attention_contract.json")) as fh:
+        contract = json.load(fh)
+    worst, checked = 0.0, set()
+    for name in meta["cases"]:
+        cls = contract[name]["class"]
+        for geom in meta["geometries"]:
+            key = f"{name}/{geom}::"
+            p64 = {k[len(key) + len("param::"):]: torch.from_numpy(z[k]).double().requires_grad_(True)
+                   for k in z.files if k.startswith(key + "param::")}
+            in64 = [torch.from_numpy(z[key + k]).double().requires_grad_(True) for k in ARGS[cls]]
+            out, weights = _module64(cls, p64, in64, torch.from_numpy(z[key + "mask"]))
+            loss = (out * torch.from_numpy(z[key + "gout"]).double()).sum()
+            if weights is not None:
+                loss = loss + (weights * torch.from_numpy(z[key + "gweights"]).double()).sum()
+            loss.backward()
+            checks = [("out", out, 1e-4)] + ([("weights", weights, 1e-4)] if weights is not None else [])
+            checks += [("grad::" + k, t.grad, 1e-5) for k, t in zip(ARGS[cls], in64)]
+            checks += [("grad::" + k, t.grad, 1e-5) for k, t in p64.items()]
+            for k, got, atol in checks:
+                worst = max(worst, golden_ratio(got, z[key + k], atol, 1e-4, key + k))
+                checked.add(key + k)
+    recorded = {k for k in z.files if k.split("::", 1)[-1].split("::")[0] in ("out", "weights", "grad")}
+    assert checked == recorded, sorted(recorded ^ checked)
+    print(f"g12_attention.npz: worst ratio of the bound {worst:.3f}")

@@ -1,14 +1,18 @@
 """CPU-side checks of the graph encoders GraphAttentionLayer / GAT / GCN (Models/BiDAF/wrapper.py:7-151): the install()
 shim exports them under the reference's module path, and their constructors build the reference's state_dict (names,
-shapes) and init distributions, for every configuration captured in tests/golden/encoder_contract.json."""
+shapes) and init distributions, for every configuration captured in tests/golden/encoder_contract.json; the float64
+restatements the GPU tests compare the kernels with (tests/util.py) reproduce the golden archives on their own."""
 import json
 import math
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
+
+from tests.util import _gat64, _gat_head64, _gcn64, golden_ratio
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -86,3 +90,48 @@ def test_gat_dropout_mask_replica_is_the_cells_mask():
     full = ops.dropout_mask_reference(1234, 2 * 3 * 4 * 5, 5, 0.4)
     assert (m.reshape(-1, 5) == full[3 * 4 * 5:]).all()
     assert 0.45 < m.mean() < 0.75
+
+
+def _restatement_against(golden_dir, npz, kinds_key):
+    """Every out / grad entry of one encoder archive against the float64 restatement of its case; (worst ratio, cases)."""
+    z = np.load(os.path.join(golden_dir, npz))
+    meta = json.loads(bytes(z["meta"]).decode())
+    contract = _contract(golden_dir)
+    worst, checked, n_cases = 0.0, set(), 0
+    for name in meta[kinds_key]:
+        c = contract[name]
+        kw = c["kwargs"]
+        for kind in meta["adj_kinds"]:
+            key = f"{name}/{kind}::"
+            p64 = {k[len(key) + len("param::"):]: torch.from_numpy(z[k]).double().requires_grad_(True)
+                   for k in z.files if k.startswith(key + "param::")}
+            x = torch.from_numpy(z[key + "x"]).double().requires_grad_(True)
+            adj = torch.from_numpy(z[key + "adj"]).double()
+            if c["class"] == "GraphAttentionLayer":
+                out = _gat_head64(x, adj, p64["W"], p64["a"], kw["alpha"], None, 0.0, "elu" if kw["concat"] else "plain")
+            elif c["class"] == "GAT":
+                out = _gat64(p64, x, adj, kw["head_num"], kw["num_layers"], kw.get("alpha", 0.2))
+            else:
+                out = _gcn64(p64, x, adj, kw["num_layers"])
+            (out * torch.from_numpy(z[key + "gout"]).double()).sum().backward()
+            checks = [("out", out, 1e-4), ("grad::x", x.grad, 1e-5)] + [("grad::" + k, t.grad, 1e-5) for k, t in p64.items()]
+            for k, got, atol in checks:
+                worst = max(worst, golden_ratio(got, z[key + k], atol, 1e-4, key + k))
+                checked.add(key + k)
+            n_cases += 1
+    prefixes = tuple(f"{name}/" for name in meta[kinds_key])
+    recorded = {k for k in z.files if k.startswith(prefixes) and k.split("::")[1] in ("out", "grad")}
+    assert checked == recorded, sorted(recorded ^ checked)
+    print(f"{npz}: worst ratio of the bound {worst:.3f}")
+    return n_cases
+
+
+def test_float64_restatements_reproduce_the_gat_goldens(golden_dir):
+    """_gat_head64 / _gat64 alone against every output and gradient of g10_gat.npz at the GPU golden test's elementwise
+    bounds (1e-4 + 1e-4 |want| outputs, 1e-5 + 1e-4 |want| gradients)."""
+    assert _restatement_against(golden_dir, "g10_gat.npz", "gat_cases") == 12
+
+
+def test_float64_restatement_reproduces_the_gcn_goldens(golden_dir):
+    """_gcn64 alone against every output and gradient of g11_gcn.npz, same bounds."""
+    assert _restatement_against(golden_dir, "g11_gcn.npz", "gcn_cases") == 4

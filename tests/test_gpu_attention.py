@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.util import _module64, _query64, _tanh64
+
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0") if torch.cuda.is_available() else None
@@ -197,36 +199,6 @@ def test_self_attention_rejects_more_than_one_head():
     m = modules.SelfAttentionICLR2017(8, 7, num_heads=3).to(DEV)
     with pytest.raises(RuntimeError, match="num_heads"):
         m(torch.randn(2, 5, 8, device=DEV), torch.ones(2, 5, device=DEV))
-
-
-# ----------------------------------------------------------------------------- float64 restatements (tests only)
-def _query64(q, right, mask):
-    s = (right @ q.unsqueeze(-1)).squeeze(-1).masked_fill(mask == 0, float("-inf"))
-    w = torch.softmax(s, dim=1)
-    return (right * w.unsqueeze(-1)).sum(1), w
-
-
-def _tanh64(pre, u, w2, mask, values):
-    t = torch.tanh(pre if u is None else pre + u.unsqueeze(1))
-    e = (t @ w2.t()).masked_fill((mask == 0).unsqueeze(-1), float("-inf"))
-    w = torch.softmax(e, dim=1)
-    return w.transpose(1, 2) @ values, w
-
-
-def _module64(cls, p, inputs, mask):
-    """The five classes in float64 on plain torch ops; p: parameters by name, inputs in forward order."""
-    if cls == "Dot":
-        return _query64(inputs[0], inputs[1], mask)
-    if cls == "BiLinear":
-        return _query64(inputs[0] @ p["W.weight"].t() + p["W.bias"], inputs[1], mask)
-    if cls == "BiLinearTanh":
-        pre = inputs[0] @ p["left_linear.weight"].t() + p["left_linear.bias"]
-        att, w = _tanh64(pre, inputs[1] @ p["right_linear.weight"].t(), p["combine.weight"], mask, inputs[0])
-        return att[:, 0], w[:, :, 0]
-    if cls == "SelfAttentionICLR2017":
-        att, _ = _tanh64(inputs[0] @ p["linear1.weight"].t(), None, p["linear2.weight"], mask, inputs[0])
-        return att[:, 0], None
-    return _tanh64(inputs[1] @ p["linear1.weight"].t(), None, p["linear2.weight"], mask, inputs[0])
 
 
 def test_backward_without_a_weights_gradient(golden_dir):

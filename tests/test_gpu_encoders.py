@@ -7,7 +7,8 @@ import os
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
+
+from tests.util import _gat64, _gat_head64, _gcn64
 
 pytestmark = pytest.mark.gpu
 
@@ -123,49 +124,6 @@ def test_dense_and_packed_adjacency_are_bit_identical(golden_dir):
         out, gx, gp = _fwd_bwd(m, x, packed, gout)
         _close(out, z[key + "out"], 1e-4, 1e-4, key + "packed out")
         _close(gx, z[key + "grad::x"], 1e-5, 1e-4, key + "packed grad::x")
-
-
-# ----------------------------------------------------------------------------- float64 restatements (tests only)
-def _gat_head64(x, adj, W, a, alpha, att_mask, p, mode):
-    """One head of wrapper.py:27-53 in float64; att_mask (B,L,L) bool of kept attention entries or None."""
-    h = x @ W
-    f = W.shape[1]
-    e = F.leaky_relu(h @ a[:f] + (h @ a[f:]).transpose(1, 2), alpha)
-    att = torch.softmax(torch.where(adj > 0, e, torch.full_like(e, -9e15)), dim=2)
-    if att_mask is not None:
-        att = att * att_mask / (1.0 - p)
-    hp = att @ h
-    return F.elu(hp) if mode == "elu" else hp
-
-
-def _gat64(params, x, adj, heads, layers, alpha, masks=None, p=0.0, relu_mask=None):
-    """GAT.forward (wrapper.py:99-110) in float64; masks: replayed (input, [per layer (H,B,L,L)], pre-output, output);
-    relu_mask: the final ReLU's decisions taken from the device run (see test_bench_scale_gat_and_gcn)."""
-    L = x.shape[1]
-    if masks is not None:
-        x = x * masks["in"] / (1.0 - p)
-    for li in range(layers - 1):
-        att = masks["att"][li] if masks is not None else None
-        x = torch.cat([_gat_head64(x, adj, params[f"layer_{li}_{j}.W"], params[f"layer_{li}_{j}.a"], alpha,
-                                   att[j] if att is not None else None, p, "elu") for j in range(heads)], dim=2)
-    if masks is not None:
-        x = x * masks["mid"] / (1.0 - p)
-    att = masks["att"][layers - 1] if masks is not None else None
-    y = sum([_gat_head64(x, adj, params[f"out_att.{j}.W"], params[f"out_att.{j}.a"], alpha,
-                         att[j] if att is not None else None, p, "plain") for j in range(heads)]) / L
-    return F.relu(y) if relu_mask is None else y * relu_mask
-
-
-def _gcn64(params, x, adj, layers, in_mask=None, p=0.0, relu_masks=None):
-    if in_mask is not None:
-        x = x * in_mask / (1.0 - p)
-    d = adj.sum(-1).pow(-0.5)
-    d[torch.isinf(d)] = 0.0
-    a_hat = d[:, :, None] * adj * d[:, None, :]
-    for k in range(layers):
-        x = (a_hat @ x) @ params[f"Linear.{k}.linear.weight"].t() + params[f"Linear.{k}.linear.bias"]
-        x = F.relu(x) if relu_masks is None else x * relu_masks[k]
-    return x
 
 
 def _params64(m):

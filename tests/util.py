@@ -3,6 +3,8 @@ import json
 import os
 
 import numpy as np
+import torch
+import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -46,3 +48,90 @@ def dense_from_coo(z, idx, fixed_length):
     a = np.zeros((fixed_length, fixed_length), np.float64)
     a[z[f"c{idx}_rows"].astype(int), z[f"c{idx}_cols"].astype(int)] = z[f"c{idx}_vals"]
     return a
+
+
+def golden_ratio(got, want, atol, rtol, what):
+    """Assert |got - want| <= atol + rtol |want| elementwise (the golden tests' bound); returns the worst ratio of it."""
+    got = torch.as_tensor(np.asarray(got.detach().cpu() if torch.is_tensor(got) else got)).double()
+    want = torch.as_tensor(np.asarray(want)).double()
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    err = (got - want).abs()
+    tol = atol + rtol * want.abs()
+    worst = (err / tol).max().item()
+    assert bool(torch.isfinite(got).all()) and bool((err <= tol).all()), \
+        f"{what}: max err {err.max().item():.3e} ({worst:.2f} x bound)"
+    return worst
+
+
+# ----------------------------------------------------------------------------- float64 restatements (tests only)
+# Plain torch statements of the attention and encoder operations, evaluated in float64 by the GPU parity tests and
+# checked on their own against the reference's goldens by tests/test_attention_cpu.py and tests/test_encoders_cpu.py.
+def _query64(q, right, mask):
+    s = (right @ q.unsqueeze(-1)).squeeze(-1).masked_fill(mask == 0, float("-inf"))
+    w = torch.softmax(s, dim=1)
+    return (right * w.unsqueeze(-1)).sum(1), w
+
+
+def _tanh64(pre, u, w2, mask, values):
+    t = torch.tanh(pre if u is None else pre + u.unsqueeze(1))
+    e = (t @ w2.t()).masked_fill((mask == 0).unsqueeze(-1), float("-inf"))
+    w = torch.softmax(e, dim=1)
+    return w.transpose(1, 2) @ values, w
+
+
+def _module64(cls, p, inputs, mask):
+    """The five classes in float64 on plain torch ops; p: parameters by name, inputs in forward order."""
+    if cls == "Dot":
+        return _query64(inputs[0], inputs[1], mask)
+    if cls == "BiLinear":
+        return _query64(inputs[0] @ p["W.weight"].t() + p["W.bias"], inputs[1], mask)
+    if cls == "BiLinearTanh":
+        pre = inputs[0] @ p["left_linear.weight"].t() + p["left_linear.bias"]
+        att, w = _tanh64(pre, inputs[1] @ p["right_linear.weight"].t(), p["combine.weight"], mask, inputs[0])
+        return att[:, 0], w[:, :, 0]
+    if cls == "SelfAttentionICLR2017":
+        att, _ = _tanh64(inputs[0] @ p["linear1.weight"].t(), None, p["linear2.weight"], mask, inputs[0])
+        return att[:, 0], None
+    return _tanh64(inputs[1] @ p["linear1.weight"].t(), None, p["linear2.weight"], mask, inputs[0])
+
+
+def _gat_head64(x, adj, W, a, alpha, att_mask, p, mode):
+    """One head of wrapper.py:27-53 in float64; att_mask (B,L,L) bool of kept attention entries or None."""
+    h = x @ W
+    f = W.shape[1]
+    e = F.leaky_relu(h @ a[:f] + (h @ a[f:]).transpose(1, 2), alpha)
+    att = torch.softmax(torch.where(adj > 0, e, torch.full_like(e, -9e15)), dim=2)
+    if att_mask is not None:
+        att = att * att_mask / (1.0 - p)
+    hp = att @ h
+    return F.elu(hp) if mode == "elu" else hp
+
+
+def _gat64(params, x, adj, heads, layers, alpha, masks=None, p=0.0, relu_mask=None):
+    """GAT.forward (wrapper.py:99-110) in float64; masks: replayed (input, [per layer (H,B,L,L)], pre-output, output);
+    relu_mask: the final ReLU's decisions taken from the device run (see test_bench_scale_gat_and_gcn)."""
+    L = x.shape[1]
+    if masks is not None:
+        x = x * masks["in"] / (1.0 - p)
+    for li in range(layers - 1):
+        att = masks["att"][li] if masks is not None else None
+        x = torch.cat([_gat_head64(x, adj, params[f"layer_{li}_{j}.W"], params[f"layer_{li}_{j}.a"], alpha,
+                                   att[j] if att is not None else None, p, "elu") for j in range(heads)], dim=2)
+    if masks is not None:
+        x = x * masks["mid"] / (1.0 - p)
+    att = masks["att"][layers - 1] if masks is not None else None
+    y = sum([_gat_head64(x, adj, params[f"out_att.{j}.W"], params[f"out_att.{j}.a"], alpha,
+                         att[j] if att is not None else None, p, "plain") for j in range(heads)]) / L
+    return F.relu(y) if relu_mask is None else y * relu_mask
+
+
+def _gcn64(params, x, adj, layers, in_mask=None, p=0.0, relu_masks=None):
+    if in_mask is not None:
+        x = x * in_mask / (1.0 - p)
+    d = adj.sum(-1).pow(-0.5)
+    d[torch.isinf(d)] = 0.0
+    a_hat = d[:, :, None] * adj * d[:, None, :]
+    for k in range(layers):
+        x = (a_hat @ x) @ params[f"Linear.{k}.linear.weight"].t() + params[f"Linear.{k}.linear.bias"]
+        x = F.relu(x) if relu_masks is None else x * relu_masks[k]
+    return x
