@@ -63,6 +63,34 @@ def golden_ratio(got, want, atol, rtol, what):
     return worst
 
 
+# ----------------------------------------------------------------------------- path-by-path parity (tests/test_gpu_*_paths.py)
+TOL = 1e-4                       # of the largest entry of the float64 result (the project's bound for restatements)
+WORST = {}                       # family -> worst observed err / scale, printed with every case
+
+
+def _rel(got, want, what, fam, floor=None):
+    """Finite and max error <= TOL of the float64 result's largest entry; prints and records the ratio.  `floor`: where
+    the float64 result is identically 0 because its terms cancel (the softmax over a single element has a zero
+    Jacobian), the size of the cancelling terms, which is what a rounding error is relative to."""
+    got = got.detach().double().cpu()
+    want = want.detach().double()
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    assert bool(torch.isfinite(got).all()), f"{what}: {int((~torch.isfinite(got)).sum())} elements not written / not finite"
+    scale = want.abs().max().item() + 1e-12
+    if floor is not None and scale <= 1e-12:      # only ever in place of a result that is identically 0
+        scale = float(floor)
+    err = (got - want).abs().max().item()
+    WORST[fam] = max(WORST.get(fam, 0.0), err / scale)
+    print(f"{what}: max err {err:.3e} over scale {scale:.3e} = {err / scale:.3e} (worst {fam}: {WORST[fam]:.3e})")
+    assert err <= TOL * scale, f"{what}: max err {err:.3e} vs scale {scale:.3e}"
+
+
+def _same(a, b, what):
+    for i, (u, v) in enumerate(zip(a, b)):
+        if u is not None:
+            assert torch.equal(u.view(torch.int32), v.view(torch.int32)), f"{what}: output {i} differs between two calls"
+
+
 # ----------------------------------------------------------------------------- float64 restatements (tests only)
 # Plain torch statements of the attention and encoder operations, evaluated in float64 by the GPU parity tests and
 # checked on their own against the reference's goldens by tests/test_attention_cpu.py and tests/test_encoders_cpu.py.
