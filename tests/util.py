@@ -163,3 +163,146 @@ def _gcn64(params, x, adj, layers, in_mask=None, p=0.0, relu_masks=None):
         x = (a_hat @ x) @ params[f"Linear.{k}.linear.weight"].t() + params[f"Linear.{k}.linear.bias"]
         x = F.relu(x) if relu_masks is None else x * relu_masks[k]
     return x
+
+
+# ----------------------------------------------------------------------------- graph restatements (numpy / float64, tests only)
+# Plain statements of what csrc/graph_ops.hip computes, used as the references of tests/test_gpu_graph_paths.py and
+# checked on their own, without any kernel, against the reference's goldens by tests/test_graph_restatements_cpu.py.
+def g_words(r):
+    return (r + 63) // 64
+
+
+def g_pack_bits(mask):
+    """bool (..., R) -> int64 (..., W) bit words, bit j & 63 of word j >> 6 = mask[..., j]; bits >= R are zero."""
+    mask = np.asarray(mask, dtype=bool)
+    r = mask.shape[-1]
+    out = np.zeros(mask.shape[:-1] + (g_words(r),), dtype=np.uint64)
+    for j in range(r):
+        out[..., j >> 6] |= mask[..., j].astype(np.uint64) << np.uint64(j & 63)
+    return out.view(np.int64)
+
+
+def g_unpack_bits(words, r):
+    """int64 / uint64 (..., W) -> bool (..., R); also returns whether any bit >= R is set."""
+    w = np.ascontiguousarray(words).view(np.uint64)
+    out = np.zeros(w.shape[:-1] + (r,), dtype=bool)
+    for j in range(r):
+        out[..., j] = ((w[..., j >> 6] >> np.uint64(j & 63)) & np.uint64(1)).astype(bool)
+    spare = np.zeros(w.shape[:-1], dtype=bool)
+    for j in range(r, 64 * w.shape[-1]):
+        spare |= ((w[..., j >> 6] >> np.uint64(j & 63)) & np.uint64(1)).astype(bool)
+    return out, bool(spare.any())
+
+
+def g_dinv(pattern):
+    """float32(1 / sqrt(float64(row degree))) of a bool pattern (..., R, R), 0 for rows without an edge."""
+    deg = np.asarray(pattern, dtype=bool).sum(-1).astype(np.float64)
+    with np.errstate(divide="ignore"):
+        return np.where(deg > 0, 1.0 / np.sqrt(deg), 0.0).astype(np.float32)
+
+
+def g_text_graphs(tokens, lengths, r, window, convert_text):
+    """Word graphs of a batch of texts from the oracle's convert_text (lengths clamped into [0, r] as gh_graph_build does):
+    node_ids int32 (n, r), n_nodes int32 (n,), pattern bool (n, r, r), dinv float32 (n, r), adj float64 (n, r, r)."""
+    n = len(tokens)
+    ids, nn = np.zeros((n, r), np.int32), np.zeros((n,), np.int32)
+    adj = np.zeros((n, r, r), np.float64)
+    for g in range(n):
+        ln = min(max(int(lengths[g]), 0), r)
+        i_, a_, k_ = convert_text([int(t) for t in tokens[g]], r, ln, window)
+        ids[g], adj[g], nn[g] = np.asarray(i_), a_, k_
+    pattern = adj != 0
+    return ids, nn, pattern, g_dinv(pattern), adj
+
+
+def g_dense_pattern(a):
+    """Pattern a dense hand-over is packed to: A's non-zeros (after the cast to fp32) united with A^T's."""
+    nz = np.asarray(a).astype(np.float32) != 0
+    return nz | np.swapaxes(nz, -1, -2)
+
+
+def g_refined64(pattern, keep=None, dinv=None, vals=None, transpose=False):
+    """float64 (n, r, r) adjacency the aggregation multiplies with: entry (i, j) is on iff pattern[i][j] and (no keep-set or
+    keep[i] or keep[j]); its value is dinv[i] dinv[j] (normalised mode) or vals[i][j] (weighted mode; A^T when `transpose`)."""
+    on = np.asarray(pattern, dtype=bool)
+    if keep is not None:
+        keep = np.asarray(keep, dtype=bool)
+        on = on & (keep[..., :, None] | keep[..., None, :])
+    if vals is not None:
+        v = np.asarray(vals, dtype=np.float32).astype(np.float64)
+        v = np.swapaxes(v, -1, -2) if transpose else v
+    else:
+        d = np.asarray(dinv, dtype=np.float32).astype(np.float64)
+        v = d[..., :, None] * d[..., None, :]
+    return np.where(on, v, 0.0)
+
+
+def g_topk(score, k):
+    """bool keep-set of the k best per row of score (..., R): descending score, ties to the lower index (-0.0 == 0.0)."""
+    s = np.asarray(score)
+    r = s.shape[-1]
+    order = np.argsort(-s.astype(np.float64), axis=-1, kind="stable")
+    keep = np.zeros(s.shape, dtype=bool)
+    kk = min(max(int(k), 0), r)
+    np.put_along_axis(keep, order[..., :kk], True, axis=-1)
+    return keep
+
+
+def g_scorer64(adj64, xproj, gate):
+    """The word scorer GGNN(h -> 1) after its projection, in float64: xproj (n, r) = proj(dropout(feat)), one aggregation
+    with the UNREFINED adjacency adj64 (n, r, r), the six 1x1 gates gate[12] = {wz0,bz0,wz1,bz1,wr0,br0,wr1,br1,wh0,bh0,wh1,bh1}."""
+    x = np.asarray(xproj, dtype=np.float64)
+    g = np.asarray(gate, dtype=np.float64)
+    a = np.einsum("nij,nj->ni", np.asarray(adj64, dtype=np.float64), x)
+    sig = lambda t: 1.0 / (1.0 + np.exp(-t))
+    z = sig((g[0] * a + g[1]) + (g[2] * x + g[3]))
+    rr = sig((g[4] * a + g[5]) + (g[6] * x + g[7]))
+    hh = np.tanh((g[8] * a + g[9]) + (g[10] * (rr * x) + g[11]))
+    return hh * z + x * (1.0 - z)
+
+
+def g_plan(n_nodes, r, node_ids=None):
+    """Node-compact plan: goff (n + 1,), rowg / src (n r,), and with node_ids cids / maskf (n r,).  Real node j of graph g is
+    row goff[g] + j; its padding nodes follow the real rows of the whole batch, graph by graph, in node order."""
+    nn = np.clip(np.asarray(n_nodes, dtype=np.int64), 0, r)
+    n = len(nn)
+    goff = np.zeros(n + 1, np.int32)
+    goff[1:] = np.cumsum(nn)
+    rowg, src = np.zeros(n * r, np.int32), np.zeros(n * r, np.int32)
+    pad = int(goff[n])
+    for g in range(n):
+        for j in range(r):
+            if j < nn[g]:
+                row = goff[g] + j
+            else:
+                row, pad = pad, pad + 1
+            rowg[row], src[row] = g, g * r + j
+    out = dict(goff=goff, rowg=rowg, src=src)
+    if node_ids is not None:
+        cids = np.asarray(node_ids, dtype=np.int32).reshape(-1)[src]
+        out.update(cids=cids, maskf=(cids >= 1).astype(np.float32))
+    return out
+
+
+def g_depad(counts, n_max, r, ids, adj):
+    """The fitter's de-padding as a loop over the claims: for every slot j < clamp(counts[c], 0, n_max), in claim order, the
+    ids narrowed to int32, the number of real nodes (id >= 1), the packed pattern, dinv, the fp32 values and the two flags
+    `bad` (ids not prefix-shaped, or an edge on a padding node) and `weighted` (not D^-1/2 A D^-1/2 of its own pattern to
+    4e-7 relative, or an entry present on one side only)."""
+    out = dict(ids=[], n_nodes=[], pattern=[], dinv=[], vals=[], bad=[], weighted=[])
+    for c, cnt in enumerate(np.asarray(counts).tolist()):
+        for j in range(min(max(int(cnt), 0), n_max)):
+            i_ = np.asarray(ids[c, j]).astype(np.int64)
+            a32 = np.asarray(adj[c, j], dtype=np.float64).astype(np.float32)
+            real = i_ >= 1
+            nn = int(real.sum())
+            pat = (a32 != 0) | (a32.T != 0)
+            dinv = g_dinv(pat)
+            bad = bool((real != (np.arange(r) < nn)).any()) or bool((pat.any(-1) & ~real).any())
+            e = (dinv[:, None] * dinv[None, :]).astype(np.float32)           # the fp32 product, as the kernel forms it
+            tol = (np.float32(4e-7) * e).astype(np.float32)
+            weighted = bool((pat & ~(np.abs(a32 - e) <= tol)).any())
+            for key, v in zip(("ids", "n_nodes", "pattern", "dinv", "vals", "bad", "weighted"),
+                              (i_.astype(np.int32), nn, pat, dinv, a32, bad, weighted)):
+                out[key].append(v)
+    return out
