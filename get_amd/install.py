@@ -26,6 +26,9 @@ def install():
     # where that module gets `nn` and `np` from
     _module("thirdparty.two_branches_attention", ConcatNotEqualSelfAtt=M.ConcatNotEqualSelfAtt,
             ConcatSelfAtt=M.ConcatSelfAtt, Dot=M.Dot, BiLinear=M.BiLinear, BiLinearTanh=M.BiLinearTanh,
+            ScaledDotProductAttention=M.ScaledDotProductAttention, MultiHeadAttentionOriginal=M.MultiHeadAttentionOriginal,
+            ConcatNotEqualSelfAttTransFormer=M.ConcatNotEqualSelfAttTransFormer,
+            MultiHeadAttentionSimple=M.MultiHeadAttentionSimple, CoDaAttention=M.CoDaAttention,
             torch=torch, nn=nn, np=np)
     _module("thirdparty.self_attention", MultiHeadSelfAttentionICLR2017Extend=M.MultiHeadSelfAttentionICLR2017Extend,
             SelfAttentionICLR2017=M.SelfAttentionICLR2017,

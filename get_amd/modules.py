@@ -6,7 +6,9 @@ load unchanged:
 
   Models/BiDAF/wrapper.py                      Linear, GGNN, GSL, GGNN_with_GSL, LSTM,
                                                GraphAttentionLayer, GAT, GCN
-  thirdparty/two_branches_attention.py         ConcatNotEqualSelfAtt, ConcatSelfAtt, Dot, BiLinear, BiLinearTanh
+  thirdparty/two_branches_attention.py         ConcatNotEqualSelfAtt, ConcatSelfAtt, Dot, BiLinear, BiLinearTanh,
+                                               ScaledDotProductAttention, MultiHeadAttentionOriginal,
+                                               ConcatNotEqualSelfAttTransFormer, MultiHeadAttentionSimple, CoDaAttention
   thirdparty/self_attention.py                 MultiHeadSelfAttentionICLR2017Extend, SelfAttentionICLR2017,
                                                MultiHeadSelfAttentionICLR17OnWord, SelfAttentionType
   Models/FCWithEvidences/graph_based_semantic_structure.py   Graph_basedSemantiStructure
@@ -494,6 +496,145 @@ class MultiHeadSelfAttentionICLR17OnWord(nn.Module):
         if return_att_weights:
             return attended, weights
         return attended
+
+
+# ------------------------------------------------------------------ thirdparty/two_branches_attention.py:391-422
+class ScaledDotProductAttention(nn.Module):
+    """softmax(query key^T) value with a bool mask (True = masked); the reference divides by no temperature (:415 is commented
+    out) and has no dropout, the two arguments are kept for the signature.  Returns (output (N,Lq,dv), attn (N,Lq,Lk)); masked
+    entries of attn are exactly 0 and a fully masked row is all zero."""
+
+    def __init__(self, temperature, attn_dropout=0.1):
+        super().__init__()
+        self.temperature = temperature
+
+    def forward(self, query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, mask=None):
+        if mask is None:
+            raise TypeError("ScaledDotProductAttention: mask is None, but the forward fills by it (two_branches_attention.py:419)")
+        _lib.require_cuda(query, key, value, mask)
+        return ops.mha_sdpa(query, key, value, mask, 1)
+
+
+# ------------------------------------------------------------------ thirdparty/two_branches_attention.py:271-347
+class MultiHeadAttentionOriginal(nn.Module):
+    """Transformer-style multi-head attention with a residual LayerNorm: q (B,Lq,D), k = v (B,Lk,D), mask (B,Lq,Lk) bool with
+    True = masked; returns (output (B,Lq,D), None).  The heads stay column slices of the three projections' outputs."""
+
+    def __init__(self, n_head, d_model, d_k, d_v, dropout=0.1):
+        super().__init__()
+        self.n_head, self.d_k, self.d_v = n_head, d_k, d_v
+        _drop_caches_on_load(self)
+        self.w_qs = nn.Linear(d_model, n_head * d_k)
+        self.w_ks = nn.Linear(d_model, n_head * d_k)
+        self.w_vs = nn.Linear(d_model, n_head * d_v)
+        self.attention = ScaledDotProductAttention(temperature=np.power(1, 1))
+        self.layer_norm = nn.LayerNorm(d_model)
+        self.fc = nn.Linear(n_head * d_v, d_model)
+
+    def forward(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: torch.Tensor = None):
+        if mask is None:
+            raise TypeError("MultiHeadAttentionOriginal: mask is None, but the forward repeats it per head (two_branches_attention.py:337)")
+        _lib.require_cuda(q, k, v, mask)
+        residual = q
+        qp = ops.linear(q, self.w_qs.weight, self.w_qs.bias)
+        kp = ops.linear(k, self.w_ks.weight, self.w_ks.bias)
+        vp = ops.linear(v, self.w_vs.weight, self.w_vs.bias)
+        output, _ = ops.mha_sdpa(qp, kp, vp, mask, self.n_head)
+        output = ops.linear(output, self.fc.weight, self.fc.bias)
+        output = ops.add_layernorm(output, residual, self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps)
+        return output, None
+
+
+# ------------------------------------------------------------------ thirdparty/two_branches_attention.py:350-388
+class ConcatNotEqualSelfAttTransFormer(nn.Module):
+    """Additive attention of one query row over `key`, averaging the separate `value`: query (B,1,X), key (B,L,D), value
+    (B,L,Dv), mask (B,1,L) bool with True = PAD (inverted relative to the other attention modules); returns
+    (attended (B,Dv,1), weights (B,L,1)).  linear1 over cat([query, key]) splits into the hoisted query branch and the key
+    branch of ops.tanh_att.  The reference's expand() admits more query rows only where they equal L and then scores row l
+    against key l; that use is not supported: a query with more than one row raises."""
+
+    def __init__(self, inp_dim: int, out_dim: int):
+        super().__init__()
+        self.inp_dim, self.out_dim = inp_dim, out_dim
+        _drop_caches_on_load(self)
+        self.linear1 = nn.Linear(inp_dim, out_dim, bias=False)
+        self.linear2 = nn.Linear(out_dim, 1, bias=False)
+
+    def forward(self, query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, mask: torch.Tensor) \
+            -> Tuple[torch.Tensor, torch.Tensor]:
+        assert query.size(0) == key.size(0), "Must same dimensions"
+        assert self.inp_dim == (query.size(-1) + key.size(-1))
+        if query.dim() != 3 or query.size(1) != 1:
+            raise RuntimeError(f"ConcatNotEqualSelfAttTransFormer: only a single query row (B,1,X) is supported, got {tuple(query.shape)}")
+        _lib.require_cuda(query, key, value, mask)
+        x = query.size(-1)
+        w1 = self.linear1.weight
+        pre = ops.linear(key, w1[:, x:])
+        u = ops.linear(query[:, 0], w1[:, :x])
+        real = mask.reshape(key.size(0), key.size(1)) == 0
+        attended, weights = ops.tanh_att(pre, u, self.linear2.weight, real, value)
+        return attended.transpose(1, 2), weights
+
+
+# ------------------------------------------------------------------ thirdparty/two_branches_attention.py:194-268
+class MultiHeadAttentionSimple(nn.Module):
+    """Multi-head additive attention of `left` (B,X) over `right` (B,L,D), mask (B,L) with 0 = pad; returns
+    (tmp (B,1,d_model), weights (num_heads*B, L, 1)), head-major.  An all-padding sequence gives NaN for that sequence."""
+
+    def __init__(self, num_heads: int, d_model: int, d_key: int, d_value: int, init_weights: bool = False,
+                 use_layer_norm: bool = False):
+        super().__init__()
+        self.num_heads = num_heads
+        self.d_model, self.d_key, self.d_value = d_model, d_key, d_value
+        assert d_model == d_key == d_value
+        self.use_layer_norm = use_layer_norm
+        _drop_caches_on_load(self)
+        self.w_qs = nn.Linear(d_model, num_heads * d_key)
+        self.w_ks = nn.Linear(d_model, num_heads * d_key)
+        self.w_vs = nn.Linear(d_model, num_heads * d_value)
+        if init_weights:
+            nn.init.normal_(self.w_qs.weight, mean=0, std=np.sqrt(2.0 / (d_model + d_key)))
+            nn.init.normal_(self.w_ks.weight, mean=0, std=np.sqrt(2.0 / (d_model + d_key)))
+            nn.init.normal_(self.w_vs.weight, mean=0, std=np.sqrt(2.0 / (d_model + d_value)))
+        self.attention_func = ConcatNotEqualSelfAttTransFormer(inp_dim=(d_key + d_key), out_dim=d_key)
+        self.fc = nn.Linear(num_heads * d_value, d_model)
+        if init_weights:
+            nn.init.xavier_normal_(self.fc.weight)
+        if use_layer_norm:
+            self.layer_norm = nn.LayerNorm(d_model)
+
+    def forward(self, left: torch.Tensor, right: torch.Tensor, mask: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        assert left.size(0) == right.size(0), "Must same dimensions"
+        assert len(left.size()) == 2 and len(right.size()) == 3
+        B, L, D = right.size()
+        assert D == self.d_model == self.d_key, "Must have same shape"
+        _lib.require_cuda(left, right, mask)
+        H, len_q = self.num_heads, 1
+        query = ops.linear(left, self.w_qs.weight, self.w_qs.bias).view(B, len_q, H, self.d_key)
+        key = ops.linear(right, self.w_ks.weight, self.w_ks.bias).view(B, L, H, self.d_key)
+        value = ops.linear(right, self.w_vs.weight, self.w_vs.bias).view(B, L, H, self.d_value)
+        # head-major (num_heads * B) sequences: the [b'][l][h] layout ops.tanh_att reads
+        q = query.permute(2, 0, 1, 3).contiguous().view(-1, len_q, self.d_key)
+        k = key.permute(2, 0, 1, 3).contiguous().view(-1, L, self.d_key)
+        v = value.permute(2, 0, 1, 3).contiguous().view(-1, L, self.d_value)
+        pad = (mask == 0).unsqueeze(1).repeat(H, 1, 1)
+        attended, attention_weights = self.attention_func(query=q, key=k, value=v, mask=pad)
+        output = attended.reshape(H, B, len_q, self.d_value).permute(1, 2, 0, 3).contiguous().view(B, len_q, -1)
+        tmp = ops.linear(output, self.fc.weight, self.fc.bias)
+        if self.use_layer_norm:
+            tmp = ops.add_layernorm(tmp, None, self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps)
+        return tmp, attention_weights
+
+
+# ------------------------------------------------------------------ thirdparty/two_branches_attention.py:425-430
+class CoDaAttention(nn.Module):
+    """The reference's empty stub: no parameters, forward returns None."""
+
+    def __init__(self, dim: int):
+        super().__init__()
+
+    def forward(self, *input):
+        return None
 
 
 def init_weights(m):

@@ -132,9 +132,10 @@ def _direct(p) -> bool:
     """True when gradients of `p` may be accumulated by the kernels straight into `p.grad` (a live view of
     the trainer's flat bucket, see dist.FlatTrainer) instead of being returned to autograd, which
     would add them there with one extra elementwise kernel per parameter."""
+    if not getattr(p, "_gh_direct_grad", False):      # (first: a non-leaf view of a weight has no .grad to ask for)
+        return False
     g = getattr(p, "grad", None)
-    return (getattr(p, "_gh_direct_grad", False) and g is not None and g.dtype == torch.float32
-            and g.is_contiguous() and g.shape == p.shape)
+    return g is not None and g.dtype == torch.float32 and g.is_contiguous() and g.shape == p.shape
 
 
 def _f32(t: torch.Tensor) -> torch.Tensor:
@@ -828,6 +829,118 @@ def tanh_att(pre, u, w2, mask, values):
     """pre (B,L,H), u (B,H) or None, w2 (C,H), mask (B,L), values (B,L,X) -> attended (B,C,X), weights (B,L,C):
     e = w2 tanh(pre + u), masked softmax over L per head, weighted sum of `values`.  Both outputs are differentiable."""
     return _TanhAtt.apply(pre, u, w2, mask, values)
+
+
+# --------------------------------------------------------------------------- multi-head query/key/value attention
+def _rows_ld(t: torch.Tensor) -> torch.Tensor:
+    """(B, L, W) fp32 whose rows the kernels can read in place: unit stride along W and row r of batch i at (i * L + r) * ld
+    -- a contiguous tensor or a column slice of one (ld = stride(1) > W); anything else is copied."""
+    if t.dtype != torch.float32:
+        t = t.float()
+    if t.is_contiguous():
+        return t
+    s0, s1, s2 = t.stride()
+    if s2 == 1 and s1 >= t.shape[2] and s0 == t.shape[1] * s1:
+        return t
+    return t.contiguous()
+
+
+def _ld(t: torch.Tensor) -> int:
+    return t.shape[2] if t.is_contiguous() else t.stride(1)
+
+
+class _MhaSdpa(torch.autograd.Function):
+    """two_branches_attention.py:334-341 + :414-421 (the head split, softmax(q k^T) v with the mask, the head merge):
+    csrc/mha_ops.hip gh_mha_sdpa_*."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, heads):
+        if mask is None:
+            raise TypeError("mha_sdpa: mask is None; a bool mask (B,Lq,Lk) is required, as the reference's masked_fill requires it")
+        _lib.require_cuda(q, k, v, mask)
+        if mask.dtype != torch.bool:
+            raise RuntimeError(f"mha_sdpa: the mask must be a bool tensor (True = masked), got {mask.dtype}")
+        assert q.dim() == 3 and k.dim() == 3 and v.dim() == 3, "mha_sdpa: q (B,Lq,H*dk), k (B,Lk,H*dk), v (B,Lk,H*dv)"
+        q, k, v = _rows_ld(q), _rows_ld(k), _rows_ld(v)
+        b, lq, wq = q.shape
+        lk, wv = k.shape[1], v.shape[2]
+        assert k.shape == (b, lk, wq) and v.shape[:2] == (b, lk) and wq % heads == 0 and wv % heads == 0 and \
+            mask.shape == (b, lq, lk), "mha_sdpa: q (B,Lq,H*dk), k (B,Lk,H*dk), v (B,Lk,H*dv), mask (B,Lq,Lk)"
+        dk, dv = wq // heads, wv // heads
+        m8 = mask.contiguous().view(torch.uint8)
+        weights = torch.empty((heads * b, lq, lk), device=q.device, dtype=torch.float32)
+        out = torch.empty((b, lq, heads * dv), device=q.device, dtype=torch.float32)
+        call("gh_mha_sdpa_fwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), _ld(q), _ld(k), _ld(v), ptr(m8), b, heads, lq, lk, dk, dv,
+             ptr(weights), ptr(out), heads * dv, stream())
+        ctx.set_materialize_grads(False)
+        ctx.dims = (b, heads, lq, lk, dk, dv)
+        ctx.save_for_backward(q, k, v, weights)
+        return out, weights
+
+    @staticmethod
+    def backward(ctx, g_out, g_w):
+        q, k, v, weights = ctx.saved_tensors
+        b, heads, lq, lk, dk, dv = ctx.dims
+        g_out = _f32(g_out) if g_out is not None else torch.zeros((b, lq, heads * dv), device=q.device)
+        g_w = _f32(g_w) if g_w is not None else None
+        ds = torch.empty_like(weights)
+        dq = torch.empty((b, lq, heads * dk), device=q.device, dtype=torch.float32)
+        dkk = torch.empty((b, lk, heads * dk), device=q.device, dtype=torch.float32)
+        dvv = torch.empty((b, lk, heads * dv), device=q.device, dtype=torch.float32)
+        call("gh_mha_sdpa_bwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), _ld(q), _ld(k), _ld(v), ptr(weights), ptr(g_out), heads * dv,
+             ptr(g_w), b, heads, lq, lk, dk, dv, ptr(ds), ptr(dq), heads * dk, ptr(dkk), heads * dk, ptr(dvv), heads * dv, stream())
+        return dq, dkk, dvv, None, None
+
+
+def mha_sdpa(q, k, v, mask, heads: int):
+    """q (B,Lq,H*dk), k (B,Lk,H*dk), v (B,Lk,H*dv) with head h in the columns [h*d, (h+1)*d) (column slices of a wider tensor
+    are read in place), mask (B,Lq,Lk) bool with True = masked, shared by the heads -> out (B,Lq,H*dv), weights (H*B,Lq,Lk) in
+    the reference's head-major order.  softmax(q_h k_h^T) without a temperature; masked weights are exactly 0, a fully masked
+    row is all zero.  Both outputs are differentiable."""
+    return _MhaSdpa.apply(q, k, v, mask, heads)
+
+
+class _AddLayerNorm(torch.autograd.Function):
+    """two_branches_attention.py:345 layer_norm(output + residual) / :267 layer_norm(tmp): gh_add_layernorm_*."""
+
+    @staticmethod
+    def forward(ctx, x, res, weight, bias, eps):
+        _lib.require_cuda(x, res, weight, bias)
+        x2 = _f32(x).reshape(-1, x.shape[-1])
+        rows, d = x2.shape
+        assert weight.shape == (d,) and bias.shape == (d,), "add_layernorm: weight (D,), bias (D,)"
+        r2 = None
+        if res is not None:
+            assert res.shape == x.shape, "add_layernorm: res has the shape of x"
+            r2 = _f32(res).reshape(rows, d)
+        wc, bc = _f32(weight.detach()), _f32(bias.detach())
+        y = torch.empty_like(x2)
+        mean = torch.empty((rows,), device=x2.device, dtype=torch.float32)
+        rstd = torch.empty_like(mean)
+        call("gh_add_layernorm_fwd", ptr(x2), ptr(r2), ptr(wc), ptr(bc), float(eps), rows, d, ptr(y), ptr(mean), ptr(rstd), stream())
+        ctx.has_res = res is not None
+        ctx.xshape = x.shape
+        ctx.save_for_backward(x2, r2, wc, mean, rstd)
+        return y.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, g):
+        x2, r2, wc, mean, rstd = ctx.saved_tensors
+        rows, d = x2.shape
+        _lib.ensure_workspace(x2.device)      # the per-workgroup dgamma / dbeta partials
+        g2 = _f32(g).reshape(rows, d)
+        dx = torch.empty_like(x2)
+        dgamma = torch.zeros((d,), device=x2.device, dtype=torch.float32)
+        dbeta = torch.zeros((d,), device=x2.device, dtype=torch.float32)
+        call("gh_add_layernorm_bwd", ptr(x2), ptr(r2), ptr(wc), ptr(mean), ptr(rstd), ptr(g2), rows, d, ptr(dx), ptr(dgamma),
+             ptr(dbeta), stream())
+        dx = dx.view(ctx.xshape)
+        return dx, (dx if ctx.has_res else None), dgamma, dbeta, None
+
+
+def add_layernorm(x, res, weight, bias, eps: float = 1e-5):
+    """LayerNorm(x + res) * weight + bias over the last axis (res may be None), biased variance."""
+    return _AddLayerNorm.apply(x, res, weight, bias, eps)
 
 
 # --------------------------------------------------------------------------- linear

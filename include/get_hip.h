@@ -373,6 +373,46 @@ int gh_tanh_att_bwd(const float* t, const float* w2, const float* weights, const
                     float* dpre, float* du /*NULL when the forward had no u*/, float* dw2 /*ACCUMULATED*/, float* dvalues,
                     gh_stream_t stream);
 
+/* ---- multi-head query/key/value attention: thirdparty/two_branches_attention.py ScaledDotProductAttention :391-422 as
+ *      MultiHeadAttentionOriginal :271-347 calls it, and the residual LayerNorm of :345 ----
+ * fp32, no floating-point atomics (two runs are bit-identical), nothing is allocated.
+ *
+ * Masked multi-head dot-product attention (:414-421; the reference divides by no temperature: softmax(q k^T)), replacing
+ * the per-operand permute(2, 0, 1, 3).contiguous() copies of :334-336, the two bmm, the softmax and both masked_fill of
+ * :414-421 and the permute copy of :340-341:
+ *   q [b][lq][heads * dk], k [b][lk][heads * dk], v [b][lk][heads * dv], row r of batch i at (i * l + r) * ld, each with its
+ *   own leading dimension (ld >= heads * width): head h is the column slice [h * width, (h + 1) * width), read in place
+ *   from the projection GEMM's output.  mask [b][lq][lk] uint8, nonzero = masked, shared by all heads.
+ *   weights [heads * b][lq][lk] (index h * b + i, the reference's order) is always written: softmax over the unmasked
+ *   keys with the running maximum subtracted, exactly 0.0 at masked positions; a query row with every key masked has
+ *   all-zero weights and an all-zero output row (never NaN).  out [b][lq][heads * dv] (leading dimension ldo) = weights v_h.
+ * Limits: 1 <= heads <= 16, lq <= 1024, lk <= 1024, dk <= 512, dv <= 512, b * ceil(max(lq, lk) / 16) < 2^31; anything
+ * beyond them is rejected with an error and nothing is written.  Rows that are 16-byte aligned (ld % 4 == 0, width % 4 ==
+ * 0, aligned base) move 16 bytes per lane, every other shape takes single-float accesses. */
+int gh_mha_sdpa_fwd(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv,
+                    const uint8_t* mask, int b, int heads, int lq, int lk, int dk, int dv,
+                    float* weights, float* out, int ldo, gh_stream_t stream);
+/* Backward of the above (autograd of :414-421 and of the permutes around it) from g_out [b][lq][heads * dv] (ldgo) and
+ * g_weights [heads * b][lq][lk] (NULL ok), with A the saved weights, per head:
+ *   dA = g_weights + g_out_h v_h^T,  dS = A (dA - rowsum(A dA)),  dq_h = dS k_h,  dk_h = dS^T q_h,  dv_h = A^T g_out_h.
+ * ds [heads * b][lq][lk] is scratch of the caller's (it receives dS).  Every element of dq, dk and dv (layouts of q, k, v
+ * with their own leading dimensions) is written, nothing is accumulated; a fully masked query row sends exact zeros. */
+int gh_mha_sdpa_bwd(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv,
+                    const float* weights, const float* g_out, int ldgo, const float* g_weights /*NULL ok*/,
+                    int b, int heads, int lq, int lk, int dk, int dv, float* ds /*scratch*/,
+                    float* dq, int lddq, float* dk_out, int lddk, float* dv_out, int lddv, gh_stream_t stream);
+/* y [rows][d] = LayerNorm(x + res) * gamma + beta over the last axis (:345 layer_norm(output + residual); :267 with
+ * res = NULL), biased variance, eps inside the square root (nn.LayerNorm's default is 1e-5).  mean [rows] and
+ * rstd [rows] are saved for the backward.  One wave per row; needs d <= 2048. */
+int gh_add_layernorm_fwd(const float* x, const float* res /*NULL ok*/, const float* gamma, const float* beta, float eps,
+                         int rows, int d, float* y, float* mean, float* rstd, gh_stream_t stream);
+/* Backward from g [rows][d]: dx [rows][d] (also the gradient of res) is written; dgamma [d] and dbeta [d] are ACCUMULATED
+ * (+=) from per-workgroup partials ([<= 256][2][d] floats on the stream workspace, which must be registered:
+ * gh_set_stream_workspace / gh_set_workspace) summed by a second stage in workgroup order. */
+int gh_add_layernorm_bwd(const float* x, const float* res /*NULL ok*/, const float* gamma, const float* mean,
+                         const float* rstd, const float* g, int rows, int d, float* dx, float* dgamma /*ACCUMULATED*/,
+                         float* dbeta /*ACCUMULATED*/, gh_stream_t stream);
+
 /* ---- a8  ragged helpers: Models/FCWithEvidences/basic_fc_model.py:80-121 ----
  * offsets[b+1] int32 prefix sum of evidence counts (device). */
 /* has[b] (NULL ok) = 1.0 for claims with at least one evidence: row 0 of pad_right(x) is x's first row of the claim times has. */
