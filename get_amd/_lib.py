@@ -57,6 +57,8 @@ SIGNATURES = {
     "gh_mha_sdpa_bwd": [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _I, _P],
     "gh_add_layernorm_fwd": [_P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P],
     "gh_add_layernorm_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
+    "gh_lstm_seq_fwd": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P],
+    "gh_lstm_seq_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P],
     "gh_evd_assemble_fwd": [_P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "gh_evd_assemble_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "gh_clamp_events": [_P, _I],

@@ -226,17 +226,77 @@ class GGNN_with_GSL(nn.Module):
 
 # ------------------------------------------------------------------ Models/BiDAF/wrapper.py:229-276
 class LSTM(nn.Module):
-    """Present only for state_dict compatibility: BasicFCModel instantiates two of these
-    (basic_fc_model.py:49-52) but GET's forward never runs them."""
+    """The reference's LSTM sequence encoder on the HIP recurrence kernels (ops.lstm_seq).  ``self.rnn`` only holds the
+    parameters (state_dict keys ``rnn.weight_ih_l0`` ...): it is never called, neither MIOpen nor nn.LSTM.forward runs.
 
-    def __init__(self, input_size, hidden_size, batch_first=False, num_layers=1, bidirectional=False, dropout=0.2):
+    forward((x, x_len, d_new_indices, d_restoring_indices), return_h=True, max_len=None):
+      x (B,L,D) on the device; x_len (B,) any integer dtype on either device; the index pair must be inverse permutations
+      (as the reference requires); d_new_indices -- the reference's order by descending length -- only sets the order in
+      which sequences are tiled, the outputs are in the rows of x.
+      T = max_len when given (no host synchronisation then), else max(x_len) as in the reference -- one read-back when
+      x_len lives on the device.  A CPU x_len with a length < 1 or > T raises ValueError as the reference's pack / pad
+      functions do; a device x_len is clamped into [0, min(L, T)] by the kernel instead, and a length of 0 gives zero rows
+      and a zero final state (pack_padded_sequence raises there).
+      Returns y (B,T,dirs*H), zero at t >= len, and h: (B, layers*dirs*H) in the rows of x when return_h, else the raw
+      (layers*dirs, B, H) tensor in the sorted order, as the reference returns it.
+    Training mode: input dropout with the stateless mask of ops.feat_dropout, its seed kept in ``last_seed``.  There is no
+    dropout between layers (the reference passes none to nn.LSTM).  ``batch_first`` is accepted and irrelevant, as in the
+    reference, whose forward hard-codes batch-first packing."""
+
+    def __init__(self, input_size, hidden_size, batch_first=False, num_layers=1, bidirectional=False, dropout=0.2,
+                 _reset_params=True):
         super().__init__()
+        _drop_caches_on_load(self)
         self.rnn = nn.LSTM(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers,
                            bidirectional=bidirectional, batch_first=batch_first)
+        if _reset_params:       # (Graph_basedSemantiStructure keeps nn.LSTM's own init: its seeded construction must not move)
+            self.reset_params()
         self.dropout = nn.Dropout(p=dropout)
+        self.last_seed = None       # input-dropout seed of the last training-mode forward (ops.feat_dropout)
 
-    def forward(self, *a, **k):
-        raise RuntimeError("get_amd: the LSTM encoders are dead code in GET and are not part of the HIP hot path")
+    def _suffixes(self):
+        return ("", "_reverse") if self.rnn.bidirectional else ("",)
+
+    def reset_params(self):
+        for i in range(self.rnn.num_layers):
+            for sfx in self._suffixes():
+                nn.init.orthogonal_(getattr(self.rnn, "weight_hh_l%s%s" % (i, sfx)))
+                nn.init.kaiming_normal_(getattr(self.rnn, "weight_ih_l%s%s" % (i, sfx)))
+                nn.init.constant_(getattr(self.rnn, "bias_hh_l%s%s" % (i, sfx)), val=0)
+                nn.init.constant_(getattr(self.rnn, "bias_ih_l%s%s" % (i, sfx)), val=0)
+
+    def forward(self, x, return_h=True, max_len=None):
+        x, x_len, d_new_indices, d_restoring_indices = x
+        assert x.dim() == 3, "LSTM: x is (B, L, D)"
+        x_len = torch.as_tensor(x_len)
+        assert x_len.shape == (x.shape[0],) and not x_len.dtype.is_floating_point, "LSTM: x_len is an integer (B,) tensor"
+        if max_len is not None:
+            T = int(max_len)
+        else:
+            T = int(x_len.max())        # (a device x_len is read back here; the model always passes max_len)
+        if not x_len.is_cuda and (int(x_len.max()) > T or int(x_len.min()) < 1):
+            raise ValueError("LSTM: every length must lie in [1, %d], got [%d, %d]" % (T, int(x_len.min()), int(x_len.max())))
+        _lib.require_cuda(x)
+        lens = x_len.to(device=x.device, dtype=torch.int32, non_blocking=True)
+        order = torch.as_tensor(d_new_indices).to(device=x.device, dtype=torch.int32, non_blocking=True)
+        p, seed = _encoder_drop(self.training, self.dropout.p)
+        self.last_seed = seed if p > 0 else None
+        inp = ops.feat_dropout(x, p, seed)
+        states = []
+        for i in range(self.rnn.num_layers):
+            gx, w_hh = [], []
+            for sfx in self._suffixes():
+                bias = getattr(self.rnn, "bias_ih_l%s%s" % (i, sfx)) + getattr(self.rnn, "bias_hh_l%s%s" % (i, sfx))
+                gx.append(ops.linear(inp, getattr(self.rnn, "weight_ih_l%s%s" % (i, sfx)), bias))
+                w_hh.append(getattr(self.rnn, "weight_hh_l%s%s" % (i, sfx)))
+            inp, h_n, _ = ops.lstm_seq(gx, w_hh, lens, order, T)
+            states.append(h_n)
+        h = states[0] if len(states) == 1 else torch.cat(states, dim=0)
+        if return_h:
+            h = h.permute(1, 0, 2).reshape(h.shape[1], -1)
+        else:
+            h = h[:, torch.as_tensor(d_new_indices).to(x.device).long()]
+        return inp, h
 
 
 # ------------------------------------------------------------------ Models/BiDAF/wrapper.py:7-67
@@ -684,11 +744,12 @@ class Graph_basedSemantiStructure(nn.Module):
             self.article_source_embs = self._make_entity_embedding_layer(params["article_source_embeddings"], freeze=False)
             self.article_emb_size = params["article_source_embeddings"].shape[1]
         D = params["embedding_output_dim"]
-        # dead-but-present parameters of BasicFCModel.__init__ (basic_fc_model.py:49-52)
+        # the recurrent encoders of BasicFCModel.__init__ (basic_fc_model.py:49-52): GET's forward never runs them; they keep
+        # nn.LSTM's own init here so that a seeded construction of the model draws what it always drew
         self.bilstm = LSTM(input_size=D, hidden_size=H, num_layers=1, bidirectional=True, batch_first=True,
-                           dropout=self.dropout_left)
+                           dropout=self.dropout_left, _reset_params=False)
         self.query_bilstm = LSTM(input_size=D, hidden_size=H, num_layers=1, bidirectional=True, batch_first=True,
-                                 dropout=self.dropout_right)
+                                 dropout=self.dropout_right, _reset_params=False)
         # live graph encoders (:52-55)
         self.ggnn4claim_1 = GGNN(in_features=D, out_features=H)
         self.ggnn_with_gsl = GGNN_with_GSL(input_dim=D, hidden_dim=H, output_dim=H, rate=self.gsl_rate,

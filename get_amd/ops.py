@@ -943,6 +943,78 @@ def add_layernorm(x, res, weight, bias, eps: float = 1e-5):
     return _AddLayerNorm.apply(x, res, weight, bias, eps)
 
 
+# --------------------------------------------------------------------------- LSTM recurrence (wrapper.py:256-276)
+class _LstmSeq(torch.autograd.Function):
+    """One layer's recurrence, both directions in one launch: csrc/rnn_ops.hip gh_lstm_seq_*.  The weight gradient
+    dW_hh = dgates^T h_prev is ONE call of the weight-gradient GEMM per direction (gh_linear_bwd without dx)."""
+
+    @staticmethod
+    def forward(ctx, gx0, gx1, w0, w1, lens, order, t_out):
+        _lib.require_cuda(gx0, gx1, w0, w1, lens, order)
+        dirs = 1 if gx1 is None else 2
+        assert gx0.dim() == 3 and w0.dim() == 2 and (w1 is None) == (gx1 is None), "lstm_seq: gx (N,T,4H), w_hh (4H,H) per direction"
+        n, t_in, h4 = gx0.shape
+        h = w0.shape[1]
+        assert h4 == 4 * h and w0.shape[0] == h4 and (dirs == 1 or (gx1.shape == gx0.shape and w1.shape == w0.shape)), \
+            "lstm_seq: gx (N,T,4H), w_hh (4H,H) per direction"
+        assert lens.dtype == torch.int32 and lens.shape == (n,) and (order is None or (order.dtype == torch.int32 and order.shape == (n,))), \
+            "lstm_seq: lens and order are int32 (N,)"
+        gx0 = _f32(gx0)
+        gx1 = _f32(gx1) if gx1 is not None else None
+        wc0 = _f32(w0.detach())
+        wc1 = _f32(w1.detach()) if w1 is not None else None
+        lens, order = lens.contiguous(), (order.contiguous() if order is not None else None)
+        dev = gx0.device
+        y = torch.empty((n, t_out, dirs * h), device=dev, dtype=torch.float32)
+        hn = torch.empty((dirs, n, h), device=dev, dtype=torch.float32)
+        cn = torch.empty_like(hn)
+        gates = cs = hprev = None
+        if any(ctx.needs_input_grad[:4]):
+            gates = torch.empty((dirs, n, t_in, h4), device=dev, dtype=torch.float32)
+            cs = torch.empty((dirs, n, t_in, h), device=dev, dtype=torch.float32)
+            hprev = torch.empty((dirs, n, t_in, h), device=dev, dtype=torch.float32)
+        call("gh_lstm_seq_fwd", ptr(gx0), ptr(gx1), h4, ptr(wc0), ptr(wc1), ptr(lens), ptr(order), n, t_in, t_out, h, dirs, ptr(y),
+             dirs * h, ptr(gates), ptr(cs), ptr(hprev), ptr(hn), ptr(cn), stream())
+        ctx.dims = (n, t_in, t_out, h, dirs)
+        ctx.params = (w0, w1)
+        ctx.save_for_backward(wc0, wc1, lens, order, gates, cs, hprev)
+        ctx.mark_non_differentiable(cn)
+        ctx.set_materialize_grads(False)
+        return y, hn, cn
+
+    @staticmethod
+    def backward(ctx, g_y, g_hn, _g_cn):
+        wc0, wc1, lens, order, gates, cs, hprev = ctx.saved_tensors
+        n, t_in, t_out, h, dirs = ctx.dims
+        g_y = _f32(g_y) if g_y is not None else None
+        g_hn = _f32(g_hn) if g_hn is not None else None
+        dgates = torch.empty_like(gates)
+        call("gh_lstm_seq_bwd", ptr(wc0), ptr(wc1), ptr(lens), ptr(order), n, t_in, t_out, h, dirs, ptr(g_y), dirs * h, ptr(g_hn),
+             ptr(gates), ptr(cs), ptr(dgates), stream())
+        dws = [None, None]
+        for d in range(dirs):
+            if not ctx.needs_input_grad[2 + d]:
+                continue
+            _lib.ensure_workspace(dgates.device)
+            pw = ctx.params[d]
+            direct = _direct(pw)
+            dw = pw.grad if direct else torch.zeros((4 * h, h), device=dgates.device, dtype=torch.float32)
+            call("gh_linear_bwd", ptr(hprev[d]), None, None, ptr(dgates[d]), n * t_in, h, 4 * h, None, ptr(dw), None, stream())
+            dws[d] = None if direct else dw
+        return dgates[0], (dgates[1] if dirs == 2 else None), dws[0], dws[1], None, None, None
+
+
+def lstm_seq(gx, w_hh, lens, order, t_out: int):
+    """The recurrence of one LSTM layer.  gx / w_hh: one tensor per direction (forward, then reverse) -- gx (N,T_in,4H) =
+    x W_ih^T + b_ih + b_hh in torch's gate order i, f, g, o, w_hh (4H,H) as nn.LSTM stores it; lens (N,) int32 on the device
+    (clamped into [0, min(T_in, t_out)]); order (N,) int32 or None: the processing order (a permutation sorted by length keeps
+    a tile's sequences alike), outputs stay in the rows of the inputs.  Returns y (N,t_out,dirs*H) with exact zeros at
+    t >= len, h_n and c_n (dirs,N,H); y and h_n are differentiable."""
+    gx, w_hh = list(gx), list(w_hh)
+    assert len(gx) == len(w_hh) and len(gx) in (1, 2), "lstm_seq: one or two directions"
+    return _LstmSeq.apply(gx[0], gx[1] if len(gx) == 2 else None, w_hh[0], w_hh[1] if len(gx) == 2 else None, lens, order, int(t_out))
+
+
 # --------------------------------------------------------------------------- linear
 class _Linear(torch.autograd.Function):
     @staticmethod

@@ -413,6 +413,35 @@ int gh_add_layernorm_bwd(const float* x, const float* res /*NULL ok*/, const flo
                          const float* rstd, const float* g, int rows, int d, float* dx, float* dgamma /*ACCUMULATED*/,
                          float* dbeta /*ACCUMULATED*/, gh_stream_t stream);
 
+/* ---- the LSTM sequence encoder's recurrence (get_amd/csrc/rnn_ops.hip): Models/BiDAF/wrapper.py:256-276 ----
+ * What pack_padded_sequence + nn.LSTM + pad_packed_sequence + the two index gathers of :260-275 compute for ONE layer, both
+ * directions in one launch, with torch.nn.LSTM's cell equations (gate order i, f, g, o; zero initial state):
+ *   i, f, o = sigmoid(.), g = tanh(.) of gx[b][t] + h_{t-1} W_hh^T;  c_t = f c_{t-1} + i g;  h_t = o tanh(c_t)
+ * gx0 / gx1 [n][t_in][4h] (row pitch ldgx >= 4h): the input projection x W_ih^T + b_ih + b_hh of the forward / the reverse
+ * direction (gx1, w_hh1: NULL when dirs == 1), a GEMM of the caller's.  w_hh [4h][h] as nn.LSTM stores it, 16-byte aligned.
+ * lens [n] int32 on the device, clamped into [0, min(t_in, t_out)]; the reverse direction of sequence b walks t = len - 1 .. 0.
+ * order [n] (NULL = identity): slot s of the launch processes row order[s] of every tensor -- a permutation sorted by length
+ * gives the 16-sequence tiles similar lengths; an entry outside [0, n) is skipped.  Every tensor is indexed by the row b.
+ * Out: y [n][t_out][ldy] columns [dir * h, (dir + 1) * h), exact zeros at t >= len; h_n, c_n [dirs][n][h] (the state after the
+ * last step of the direction; zeros for an empty sequence -- where pack_padded_sequence raises).  gates [dirs][n][t_in][4h]
+ * (post-activation), c [dirs][n][t_in][h] and h_prev [dirs][n][t_in][h] (the hidden state that ENTERED step t, zeros at t >= len)
+ * are saved for the backward when all three are given (all NULL: inference).  Rows t >= len of gates and c are not written.
+ * The sigmoid takes exp of non-positive arguments only: saturated pre-activations give exact 0 / 1, never NaN.
+ * Limits: h <= 1024, t_in <= 4096, t_out <= 4096, dirs 1 or 2, any n; anything beyond is rejected and nothing is written. */
+int gh_lstm_seq_fwd(const float* gx0, const float* gx1 /*NULL ok*/, int ldgx, const float* w_hh0, const float* w_hh1 /*NULL ok*/,
+                    const int32_t* lens, const int32_t* order /*NULL ok*/, int n, int t_in, int t_out, int h, int dirs,
+                    float* y, int ldy, float* gates /*NULL ok*/, float* c /*NULL ok*/, float* h_prev /*NULL ok*/,
+                    float* h_n, float* c_n, gh_stream_t stream);
+/* Backward of the above (autograd of torch.nn.LSTM's cell equations, wrapper.py:256-276) from g_y [n][t_out][ldgy] (NULL ok)
+ * and g_hn [dirs][n][h] (NULL ok), walking time the other way:
+ *   dh = g_y[t] + dh_rec (+ g_hn at the direction's last step);  dc += dh o (1 - tanh(c_t)^2);  di = dc g i (1 - i);
+ *   df = dc c_{t-1} f (1 - f);  dg = dc i (1 - g^2);  do = dh tanh(c_t) o (1 - o);  dh_rec = dgates_t W_hh;  dc <- dc f
+ * dgates [dirs][n][t_in][4h] is the gradient of gx: every element is written, exact zeros at t >= len.  The caller forms
+ * dW_hh = dgates^T h_prev per direction with gh_linear_bwd (dx = NULL, x = h_prev, g = dgates).  Same limits as the forward. */
+int gh_lstm_seq_bwd(const float* w_hh0, const float* w_hh1 /*NULL ok*/, const int32_t* lens, const int32_t* order /*NULL ok*/,
+                    int n, int t_in, int t_out, int h, int dirs, const float* g_y /*NULL ok*/, int ldgy,
+                    const float* g_hn /*NULL ok*/, const float* gates, const float* c, float* dgates, gh_stream_t stream);
+
 /* ---- a8  ragged helpers: Models/FCWithEvidences/basic_fc_model.py:80-121 ----
  * offsets[b+1] int32 prefix sum of evidence counts (device). */
 /* has[b] (NULL ok) = 1.0 for claims with at least one evidence: row 0 of pad_right(x) is x's first row of the claim times has. */
