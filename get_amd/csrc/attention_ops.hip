@@ -9,6 +9,7 @@
 // library's GEMMs (gh_linear_fwd / gh_linear_bwd).
 #include "../../include/get_hip.h"
 #include "common.h"
+#include "device_utils.h"
 #include <math.h>
 
 namespace gh {
@@ -20,17 +21,6 @@ constexpr int QATT_MAX_L = 4096;         // raw scores of one sequence in LDS
 constexpr int QATT_MAX_D = 2048;         // one row of `right` in a wave's registers (8 x float4 per lane)
 constexpr int TATT_MAX_HEADS = 8;
 constexpr int TATT_MAX_LH = 8192;        // l * heads scores of one sequence in LDS (32 KB)
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // V consecutive floats of a row: V = 4 moves 16 bytes per lane (width % 4 == 0, 16-byte aligned operands), V = 1 is the
 // scalar path for every other shape
@@ -538,8 +528,6 @@ sum_partials_kernel(const float* __restrict__ part, int nb, int n, float* __rest
   __syncthreads();
   if (kl == 0 && i < n) out[i] += ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 int query_check(const char* who, int b, int l, int d) {
   GH_REQUIRE(b > 0 && l > 0 && d > 0, "%s: b=%d l=%d d=%d must be positive", who, b, l, d);

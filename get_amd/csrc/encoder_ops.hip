@@ -4,6 +4,7 @@
 // the library's grouped GEMMs (gh_linear_fwd / gh_linear_bwd), the GCN aggregation on the fp32 gh_spmm.
 #include "../../include/get_hip.h"
 #include "common.h"
+#include "device_utils.h"
 #include "gemm.hip.h"
 #include <math.h>
 
@@ -26,12 +27,6 @@ struct GatArgs {
   float drop_scale;
   int drop;
 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // LDS image of one graph (dynamic shared memory, the same layout in both kernels):
 //   rb[R][W] refined bit rows: edge (i,j) <=> bit && (keep_i || keep_j) && (vals == NULL || vals[i][j] > 0)   (wrapper.py:39)
@@ -575,13 +570,6 @@ GatArgs gat_args(const uint64_t* bits, const float* vals, const uint64_t* keep, 
   return A;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-template <typename K>
-void set_lds_cap(K kernel, size_t lds) {
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-
 }  // namespace
 }  // namespace gh
 
@@ -601,10 +589,10 @@ extern "C" int gh_gat_layer_fwd(const uint64_t* bits, const float* vals, const u
   const size_t lds = gat_lds_bytes(r, heads, 0);
   const bool v4 = f % 4 == 0 && aligned16(h) && aligned16(hp) && aligned16(out);
   if (v4) {
-    set_lds_cap(gat_aggregate_fwd_kernel<4>, lds);
+    if (int rc = lds_opt_in(gat_aggregate_fwd_kernel<4>, lds, "gat_layer_fwd")) return rc;
     hipLaunchKernelGGL(gat_aggregate_fwd_kernel<4>, dim3(n), dim3(256), lds, st, A, h, a, mode, s, stats, hp, out);
   } else {
-    set_lds_cap(gat_aggregate_fwd_kernel<1>, lds);
+    if (int rc = lds_opt_in(gat_aggregate_fwd_kernel<1>, lds, "gat_layer_fwd")) return rc;
     hipLaunchKernelGGL(gat_aggregate_fwd_kernel<1>, dim3(n), dim3(256), lds, st, A, h, a, mode, s, stats, hp, out);
   }
   GH_LAUNCH_CHECK();
@@ -624,8 +612,7 @@ extern "C" int gh_gat_layer_bwd(const uint64_t* bits, const float* vals, const u
   const int F = heads * f, m = n * r;
   const GatArgs A = gat_args(bits, vals, keep, n, r, heads, f, alpha, layer, drop_p, drop_seed);
   const size_t lds = gat_lds_bytes(r, heads, F);
-  GH_REQUIRE(lds <= 160 * 1024, "gat_layer_bwd: %zu bytes of LDS per graph (r=%d, %d heads x %d)", lds, r, heads, f);
-  set_lds_cap(gat_aggregate_bwd_kernel<1>, lds);
+  if (int rc = lds_opt_in(gat_aggregate_bwd_kernel<1>, lds, "gat_layer_bwd")) return rc;
   hipLaunchKernelGGL(gat_aggregate_bwd_kernel<1>, dim3(n), dim3(256), lds, st, A, h, a, mode, s, stats, hp, out, g, dh, da_part);
   GH_LAUNCH_CHECK();
   const int K = heads * 2 * f;

@@ -22,12 +22,11 @@
 // Every output element has one owner, nothing is accumulated in memory, no atomics: two runs are bit-identical.
 #include "../../include/get_hip.h"
 #include "common.h"
+#include "device_utils.h"
 #include <math.h>
 
 namespace gh {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int MHA_THREADS = 256;
 constexpr int MHA_WAVES = MHA_THREADS / 64;
@@ -40,9 +39,6 @@ constexpr int MHA_CHUNK = 9216;          // floats of one staged operand chunk (
 constexpr int LN_MAX_D = 2048;           // per-wave dgamma / dbeta partials in LDS: 4 x 2 x d floats
 constexpr int LN_MAX_WG = 256;
 
-__host__ __device__ inline int up4(int n) { return (n + 3) & ~3; }
-__host__ __device__ inline int up16(int n) { return (n + 15) & ~15; }
-__host__ __device__ inline int pitch_kc(int n) { n = up4(n); return (n & 7) == 4 ? n : n + 4; }
 __host__ __device__ inline int pitch_km(int n) { n = up16(n); return (n & 31) == 16 ? n : n + 16; }
 // rows of a chunk with `pitch` floats per row: a multiple of 16, at least 16, at most the padded extent
 __host__ __device__ inline int chunk_rows(int extent, int pitch, int budget) {
@@ -165,17 +161,6 @@ __device__ __forceinline__ void store_acc(float* __restrict__ dst, long long ld,
         if (4 * qd + r < rows) dst[(size_t)(4 * qd + r) * ld + c] = acc[t][r];
     }
   }
-}
-
-__device__ __forceinline__ float sub16_sum(float v) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float sub16_max(float v) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
 }
 
 // ============================================================================ forward
@@ -347,12 +332,6 @@ mha_bwd_k_kernel(const float* __restrict__ q, long long ldq, const float* __rest
 }
 
 // ============================================================================ add + LayerNorm
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // one wave per row; grid-stride over the rows
 __global__ __launch_bounds__(MHA_THREADS) void
 add_ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ res, const float* __restrict__ gamma,
@@ -364,13 +343,13 @@ add_ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ res, co
     const float* rr = res ? res + r * d : nullptr;
     float s = 0.f;
     for (int c = lane; c < d; c += 64) s += xr[c] + (rr ? rr[c] : 0.f);
-    const float mu = wave_sum64(s) / (float)d;
+    const float mu = wave_sum(s) / (float)d;
     float s2 = 0.f;
     for (int c = lane; c < d; c += 64) {
       const float z = xr[c] + (rr ? rr[c] : 0.f) - mu;
       s2 = fmaf(z, z, s2);
     }
-    const float rs = 1.f / sqrtf(wave_sum64(s2) / (float)d + eps);
+    const float rs = 1.f / sqrtf(wave_sum(s2) / (float)d + eps);
     for (int c = lane; c < d; c += 64) {
       const float z = xr[c] + (rr ? rr[c] : 0.f) - mu;
       y[r * d + c] = fmaf(z * rs, gamma[c], beta[c]);
@@ -405,8 +384,8 @@ add_ln_bwd_kernel(const float* __restrict__ x, const float* __restrict__ res, co
       c1 += dxh;
       c2 = fmaf(dxh, xh, c2);
     }
-    c1 = wave_sum64(c1) / (float)d;
-    c2 = wave_sum64(c2) / (float)d;
+    c1 = wave_sum(c1) / (float)d;
+    c2 = wave_sum(c2) / (float)d;
     for (int c = lane; c < d; c += 64) {
       const float xh = (xr[c] + (rr ? rr[c] : 0.f) - mu) * rs;
       const float gv = gr[c];
@@ -451,12 +430,6 @@ int mha_check(const char* who, int b, int heads, int lq, int lk, int dk, int dv)
   return 0;
 }
 
-template <typename K> int big_lds(K kernel, size_t lds, const char* who) {
-  GH_REQUIRE(lds <= 160 * 1024, "%s: needs %zu bytes of LDS", who, lds);
-  if (lds > 64 * 1024) GH_CHECK_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  return 0;
-}
-
 }  // namespace
 }  // namespace gh
 
@@ -470,7 +443,7 @@ extern "C" int gh_mha_sdpa_fwd(const float* q, const float* k, const float* v, i
   GH_REQUIRE(ldq >= heads * dk && ldk >= heads * dk && ldv >= heads * dv && ldo >= heads * dv,
              "mha_sdpa_fwd: a leading dimension is smaller than heads * width");
   const size_t lds = (size_t)fwd_lds_floats(fwd_plan(lk, dk, dv)) * sizeof(float);
-  if (int rc = big_lds(mha_fwd_kernel, lds, "mha_sdpa_fwd")) return rc;
+  if (int rc = lds_opt_in(mha_fwd_kernel, lds, "mha_sdpa_fwd")) return rc;
   hipLaunchKernelGGL(mha_fwd_kernel, dim3(b * ((lq + 15) / 16), heads), dim3(MHA_THREADS), lds, st, q, k, v, (long long)ldq,
                      (long long)ldk, (long long)ldv, mask, b, lq, lk, dk, dv, weights, out, (long long)ldo);
   GH_LAUNCH_CHECK();
@@ -488,8 +461,8 @@ extern "C" int gh_mha_sdpa_bwd(const float* q, const float* k, const float* v, i
              "mha_sdpa_bwd: a leading dimension is smaller than heads * width");
   const size_t lds_q = (size_t)fwd_lds_floats(fwd_plan(lk, dv, dk)) * sizeof(float);
   const size_t lds_k = (size_t)key_lds_floats(key_plan(lq, dk, dv)) * sizeof(float);
-  if (int rc = big_lds(mha_bwd_q_kernel, lds_q, "mha_sdpa_bwd")) return rc;
-  if (int rc = big_lds(mha_bwd_k_kernel, lds_k, "mha_sdpa_bwd")) return rc;
+  if (int rc = lds_opt_in(mha_bwd_q_kernel, lds_q, "mha_sdpa_bwd")) return rc;
+  if (int rc = lds_opt_in(mha_bwd_k_kernel, lds_k, "mha_sdpa_bwd")) return rc;
   hipLaunchKernelGGL(mha_bwd_q_kernel, dim3(b * ((lq + 15) / 16), heads), dim3(MHA_THREADS), lds_q, st, k, v, (long long)ldk,
                      (long long)ldv, weights, g_out, (long long)ldgo, g_weights, b, lq, lk, dk, dv, ds, dq, (long long)lddq);
   hipLaunchKernelGGL(mha_bwd_k_kernel, dim3(b * ((lk + 15) / 16), heads), dim3(MHA_THREADS), lds_k, st, q, (long long)ldq, weights,

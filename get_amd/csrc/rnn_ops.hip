@@ -20,12 +20,11 @@
 // Every output element has one owner, nothing is accumulated in memory, no atomics: two runs are bit-identical.
 #include "../../include/get_hip.h"
 #include "common.h"
+#include "device_utils.h"
 #include <math.h>
 
 namespace gh {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int RNN_THREADS = 512;
 constexpr int RNN_WAVES = RNN_THREADS / 64;
@@ -38,8 +37,7 @@ constexpr int RNN_BWD_NP = RNN_MAX_H / RNN_CHUNK;            // column groups pe
 constexpr int RNN_BWD_PF = 2;                                // k steps (of 4) whose operands are fetched ahead (backward)
 constexpr int RNN_DG_PITCH = 4 * RNN_CHUNK + 4;              // [16][4][256] + 4: rows start 4 banks apart
 
-__host__ __device__ inline int rnn_up16(int n) { return (n + 15) & ~15; }
-__host__ __device__ inline int rnn_pitch(int h) { const int n = rnn_up16(h); return (n & 7) == 4 ? n : n + 4; }
+__host__ __device__ inline int rnn_pitch(int h) { return pitch_kc(up16(h)); }      // LDS row pitch of the h_{t-1} / w_hh tiles
 
 // never overflows: exp of a non-positive argument only
 __device__ __forceinline__ float rnn_sigmoid(float x) {
@@ -144,7 +142,7 @@ lstm_fwd_kernel(const float* __restrict__ gx0, const float* __restrict__ gx1, lo
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, qd = lane >> 4;
   const bool vec = (h & 3) == 0;
   const int h4 = 4 * h;
-  const int kp = rnn_up16(h), nut = kp >> 4;
+  const int kp = up16(h), nut = kp >> 4;
 
   const int tmax = tile_setup(s_len, s_row, lens, order, n, min(t_in, t_out));
   for (int idx = threadIdx.x; idx < 2 * RNN_TILE * pitch; idx += RNN_THREADS) hs[idx] = 0.f;
@@ -375,14 +373,6 @@ int lstm_check(const char* who, int n, int t_in, int t_out, int h, int dirs) {
   return 0;
 }
 
-template <typename K> int rnn_lds(K kernel, size_t lds, const char* who) {
-  GH_REQUIRE(lds <= 160 * 1024, "%s: needs %zu bytes of LDS", who, lds);
-  if (lds > 64 * 1024) GH_CHECK_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  return 0;
-}
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 }  // namespace gh
 
@@ -399,7 +389,7 @@ extern "C" int gh_lstm_seq_fwd(const float* gx0, const float* gx1, int ldgx, con
   GH_REQUIRE(ldgx >= 4 * h && ldy >= dirs * h, "lstm_seq_fwd: a leading dimension is smaller than its row");
   GH_REQUIRE(aligned16(w_hh0) && aligned16(w_hh1), "lstm_seq_fwd: w_hh must be 16-byte aligned");
   const size_t lds = ((size_t)2 * RNN_TILE * rnn_pitch(h) + 2 * RNN_TILE) * sizeof(float);
-  if (int rc = rnn_lds(lstm_fwd_kernel, lds, "lstm_seq_fwd")) return rc;
+  if (int rc = lds_opt_in(lstm_fwd_kernel, lds, "lstm_seq_fwd")) return rc;
   hipLaunchKernelGGL(lstm_fwd_kernel, dim3((n + RNN_TILE - 1) / RNN_TILE, dirs), dim3(RNN_THREADS), lds, st, gx0, gx1, (long long)ldgx,
                      w_hh0, w_hh1, lens, order, n, t_in, t_out, h, y, (long long)ldy, gates, c, h_prev, h_n, c_n);
   GH_LAUNCH_CHECK();
@@ -415,7 +405,7 @@ extern "C" int gh_lstm_seq_bwd(const float* w_hh0, const float* w_hh1, const int
   GH_REQUIRE(!g_y || ldgy >= dirs * h, "lstm_seq_bwd: ldgy is smaller than dirs * h");
   GH_REQUIRE(aligned16(w_hh0) && aligned16(w_hh1), "lstm_seq_bwd: w_hh must be 16-byte aligned");
   const size_t lds = ((size_t)RNN_TILE * RNN_DG_PITCH + 2 * RNN_TILE) * sizeof(float);
-  if (int rc = rnn_lds(lstm_bwd_kernel, lds, "lstm_seq_bwd")) return rc;
+  if (int rc = lds_opt_in(lstm_bwd_kernel, lds, "lstm_seq_bwd")) return rc;
   hipLaunchKernelGGL(lstm_bwd_kernel, dim3((n + RNN_TILE - 1) / RNN_TILE, dirs), dim3(RNN_THREADS), lds, st, w_hh0, w_hh1, lens, order, n,
                      t_in, t_out, h, g_y, (long long)ldgy, g_hn, gates, c, dgates);
   GH_LAUNCH_CHECK();

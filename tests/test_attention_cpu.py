@@ -3,29 +3,15 @@ BiLinearTanh; thirdparty/self_attention.py SelfAttentionICLR2017, MultiHeadSelfA
 the install() shim exports them under the reference's module paths, their constructors build the reference's state_dict
 for every configuration captured in tests/golden/attention_contract.json, the golden archive is complete, and the float64
 restatements the GPU tests compare the kernels with (tests/util.py) reproduce that archive on their own."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
 
-from tests.util import _module64, golden_ratio
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.util import _module64, golden_ratio, load_golden, run_in_fresh_interpreter
 
 
 def test_install_shim_exports_the_attention_ablations(tmp_path):
-    os.makedirs(os.path.join(tmp_path, "thirdparty"), exist_ok=True)
-    open(os.path.join(tmp_path, "thirdparty", "__init__.py"), "w").close()
-    code = r"""
-import sys
-sys.path.insert(0, %r)
-sys.path.insert(0, %r)
-import get_amd
-M = get_amd.install()
+    run_in_fresh_interpreter(tmp_path, r"""
 from thirdparty.two_branches_attention import Dot, BiLinear, BiLinearTanh, ConcatNotEqualSelfAtt, ConcatSelfAtt
 from thirdparty.self_attention import (SelfAttentionICLR2017, MultiHeadSelfAttentionICLR17OnWord, SelfAttentionType,
                                        MultiHeadSelfAttentionICLR2017Extend)
@@ -37,16 +23,12 @@ assert ConcatNotEqualSelfAtt is modules.ConcatNotEqualSelfAtt and ConcatSelfAtt 
 assert MultiHeadSelfAttentionICLR2017Extend is modules.MultiHeadSelfAttentionICLR2017Extend
 assert int(SelfAttentionType.MultiHeadAttentionTanh) == 1 and int(SelfAttentionType.MultiHeadAttentionTransformer) == 2
 assert [t.name for t in SelfAttentionType] == ['MultiHeadAttentionTanh', 'MultiHeadAttentionTransformer']
-print('ok')
-""" % (ROOT, str(tmp_path))
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stderr[-2000:]
+""")
 
 
 def test_attention_state_dicts_match_the_reference_contract(golden_dir):
     from get_amd import modules
-    with open(os.path.join(golden_dir, "attention_contract.json")) as fh:
-        contract = json.load(fh)
+    _, _, contract = load_golden(golden_dir, "g12_attention.npz", "attention_contract.json")
     assert {c["class"] for c in contract.values()} == {"Dot", "BiLinear", "BiLinearTanh", "SelfAttentionICLR2017",
                                                        "MultiHeadSelfAttentionICLR17OnWord"}
     for name, c in contract.items():
@@ -79,17 +61,15 @@ def test_attention_modules_refuse_cpu_tensors():
 
 
 def test_attention_golden_archive_is_complete(golden_dir):
-    z = np.load(os.path.join(golden_dir, "g12_attention.npz"))
-    meta = json.loads(bytes(z["meta"]).decode())
+    z, meta, contract = load_golden(golden_dir, "g12_attention.npz", "attention_contract.json")
     assert set(meta["cases"]) == {"dot_d6", "dot_d8", "bilinear", "bilineartanh", "selfatt", "onword_h1", "onword_h3",
                                   "dot_offset_pos", "dot_offset_neg"}
     assert meta["geometries"] == {"b3l12": [3, 12], "b2l70": [2, 70]}
-    with open(os.path.join(golden_dir, "attention_contract.json")) as fh:
-        assert set(json.load(fh)) == set(meta["cases"])
+    assert set(contract) == set(meta["cases"])
     for name in meta["cases"]:
         for geom, (b, l) in meta["geometries"].items():
             key = f"{name}/{geom}::"
-            have = {k[len(key):] for k in z.files if k.startswith(key)}
+            have = {k[len(key):] for k in z if k.startswith(key)}
             assert {"mask", "out", "gout"} <= have, key
             assert z[key + "mask"].shape == (b, l)
             if name != "selfatt":          # the only class that returns no weights
@@ -100,7 +80,7 @@ def test_attention_golden_archive_is_complete(golden_dir):
                     assert "grad::" + k[len("param::"):] in have, key + k
             inputs = have - {"mask", "out", "gout", "weights", "gweights"} - {k for k in have if "::" in k}
             assert inputs and all("grad::" + k in have for k in inputs), (key, inputs)
-    for k in z.files:
+    for k in z:
         if k != "meta":
             assert np.isfinite(z[k]).all(), k
 
@@ -113,17 +93,14 @@ def test_float64_restatements_reproduce_the_attention_goldens(golden_dir):
     """_query64 / _tanh64 / _module64 alone, in float64 on the archive's inputs and parameters, against every captured
     output, weight and gradient at the GPU golden test's elementwise bounds (1e-4 + 1e-4 |want| for outputs and weights,
     1e-5 + 1e-4 |want| for gradients), the offset cases included."""
-    z = np.load(os.path.join(golden_dir, "g12_attention.npz"))
-    meta = json.loads(bytes(z["meta"]).decode())
-    with open(os.path.join(golden_dir, "attention_contract.json")) as fh:
-        contract = json.load(fh)
+    z, meta, contract = load_golden(golden_dir, "g12_attention.npz", "attention_contract.json")
     worst, checked = 0.0, set()
     for name in meta["cases"]:
         cls = contract[name]["class"]
         for geom in meta["geometries"]:
             key = f"{name}/{geom}::"
             p64 = {k[len(key) + len("param::"):]: torch.from_numpy(z[k]).double().requires_grad_(True)
-                   for k in z.files if k.startswith(key + "param::")}
+                   for k in z if k.startswith(key + "param::")}
             in64 = [torch.from_numpy(z[key + k]).double().requires_grad_(True) for k in ARGS[cls]]
             out, weights = _module64(cls, p64, in64, torch.from_numpy(z[key + "mask"]))
             loss = (out * torch.from_numpy(z[key + "gout"]).double()).sum()
@@ -136,6 +113,6 @@ def test_float64_restatements_reproduce_the_attention_goldens(golden_dir):
             for k, got, atol in checks:
                 worst = max(worst, golden_ratio(got, z[key + k], atol, 1e-4, key + k))
                 checked.add(key + k)
-    recorded = {k for k in z.files if k.split("::", 1)[-1].split("::")[0] in ("out", "weights", "grad")}
+    recorded = {k for k in z if k.split("::", 1)[-1].split("::")[0] in ("out", "weights", "grad")}
     assert checked == recorded, sorted(recorded ^ checked)
     print(f"g12_attention.npz: worst ratio of the bound {worst:.3f}")

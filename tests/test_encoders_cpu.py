@@ -2,44 +2,24 @@
 shim exports them under the reference's module path, and their constructors build the reference's state_dict (names,
 shapes) and init distributions, for every configuration captured in tests/golden/encoder_contract.json; the float64
 restatements the GPU tests compare the kernels with (tests/util.py) reproduce the golden archives on their own."""
-import json
 import math
-import os
-import subprocess
-import sys
 
-import numpy as np
-import pytest
 import torch
 
-from tests.util import _gat64, _gat_head64, _gcn64, golden_ratio
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.util import _gat64, _gat_head64, _gcn64, golden_ratio, load_golden, run_in_fresh_interpreter
 
 
 def _contract(golden_dir):
-    with open(os.path.join(golden_dir, "encoder_contract.json")) as fh:
-        return json.load(fh)
+    return load_golden(golden_dir, "g11_gcn.npz", "encoder_contract.json")[2]
 
 
 def test_install_shim_exports_the_encoders(tmp_path):
-    for pkg in ("Models", "Models/BiDAF"):
-        os.makedirs(os.path.join(tmp_path, pkg), exist_ok=True)
-        open(os.path.join(tmp_path, pkg, "__init__.py"), "w").close()
-    code = r"""
-import sys
-sys.path.insert(0, %r)
-sys.path.insert(0, %r)
-import get_amd
-M = get_amd.install()
+    run_in_fresh_interpreter(tmp_path, r"""
 from Models.BiDAF.wrapper import GAT, GCN, GraphAttentionLayer, Linear
 from get_amd import modules
 assert GAT is modules.GAT and GCN is modules.GCN and GraphAttentionLayer is modules.GraphAttentionLayer
 assert Linear is modules.Linear
-print('ok')
-""" % (ROOT, str(tmp_path))
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stderr[-2000:]
+""", packages=("Models", "Models/BiDAF"))
 
 
 def test_encoder_state_dicts_match_the_reference_contract(golden_dir):
@@ -94,9 +74,7 @@ def test_gat_dropout_mask_replica_is_the_cells_mask():
 
 def _restatement_against(golden_dir, npz, kinds_key):
     """Every out / grad entry of one encoder archive against the float64 restatement of its case; (worst ratio, cases)."""
-    z = np.load(os.path.join(golden_dir, npz))
-    meta = json.loads(bytes(z["meta"]).decode())
-    contract = _contract(golden_dir)
+    z, meta, contract = load_golden(golden_dir, npz, "encoder_contract.json")
     worst, checked, n_cases = 0.0, set(), 0
     for name in meta[kinds_key]:
         c = contract[name]
@@ -104,7 +82,7 @@ def _restatement_against(golden_dir, npz, kinds_key):
         for kind in meta["adj_kinds"]:
             key = f"{name}/{kind}::"
             p64 = {k[len(key) + len("param::"):]: torch.from_numpy(z[k]).double().requires_grad_(True)
-                   for k in z.files if k.startswith(key + "param::")}
+                   for k in z if k.startswith(key + "param::")}
             x = torch.from_numpy(z[key + "x"]).double().requires_grad_(True)
             adj = torch.from_numpy(z[key + "adj"]).double()
             if c["class"] == "GraphAttentionLayer":
@@ -120,7 +98,7 @@ def _restatement_against(golden_dir, npz, kinds_key):
                 checked.add(key + k)
             n_cases += 1
     prefixes = tuple(f"{name}/" for name in meta[kinds_key])
-    recorded = {k for k in z.files if k.startswith(prefixes) and k.split("::")[1] in ("out", "grad")}
+    recorded = {k for k in z if k.startswith(prefixes) and k.split("::")[1] in ("out", "grad")}
     assert checked == recorded, sorted(recorded ^ checked)
     print(f"{npz}: worst ratio of the bound {worst:.3f}")
     return n_cases

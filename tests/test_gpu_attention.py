@@ -3,14 +3,10 @@ MultiHeadSelfAttentionICLR17OnWord (get_amd.modules, ops.query_att / ops.tanh_at
 reference's captured outputs and gradients (tests/golden/g12_attention.npz), the padding and all-masked conventions, the
 weights-gradient-free backward, the project's word- and evidence-level shapes against float64 restatements, and the
 documented length limits."""
-import json
-import os
-
-import numpy as np
 import pytest
 import torch
 
-from tests.util import _module64, _query64, _tanh64
+from tests.util import _module64, _query64, _tanh64, build_from_contract, golden_ratio, load_golden, rel_close
 
 pytestmark = pytest.mark.gpu
 
@@ -22,26 +18,13 @@ CASES = ["dot_d6", "dot_d8", "bilinear", "bilineartanh", "selfatt", "onword_h1",
 ARGS = {"Dot": ("left", "right"), "BiLinear": ("left", "right"), "BiLinearTanh": ("left_tsr", "right_tsr"),
         "SelfAttentionICLR2017": ("tsr",), "MultiHeadSelfAttentionICLR17OnWord": ("original", "tsr")}
 
-_GOLDEN = {}
-
 
 def _golden(golden_dir):
-    """The archive, its meta and the constructor contract, loaded once and never modified."""
-    if not _GOLDEN:
-        z = np.load(os.path.join(golden_dir, "g12_attention.npz"))
-        _GOLDEN["z"] = {k: z[k] for k in z.files}
-        _GOLDEN["meta"] = json.loads(bytes(z["meta"]).decode())
-        with open(os.path.join(golden_dir, "attention_contract.json")) as fh:
-            _GOLDEN["contract"] = json.load(fh)
-    return _GOLDEN["z"], _GOLDEN["meta"], _GOLDEN["contract"]
+    return load_golden(golden_dir, "g12_attention.npz", "attention_contract.json")
 
 
 def _build(z, key, c):
-    from get_amd import modules
-    m = getattr(modules, c["class"])(**c["kwargs"])
-    sd = {k[len(key) + len("param::"):]: torch.from_numpy(z[k]) for k in z if k.startswith(key + "param::")}
-    m.load_state_dict(sd, strict=True)
-    return m.to(DEV)
+    return build_from_contract(z, key, c).to(DEV)
 
 
 def _forward(m, cls, inputs, mask):
@@ -50,27 +33,6 @@ def _forward(m, cls, inputs, mask):
         return m(*inputs, mask, return_att_weights=True)
     out = m(*inputs, mask)
     return out if isinstance(out, tuple) else (out, None)
-
-
-def _err(got, want):
-    got = got.detach().double().cpu()
-    want = torch.as_tensor(np.asarray(want.detach().cpu() if torch.is_tensor(want) else want)).double()
-    assert got.shape == want.shape, (got.shape, want.shape)
-    return (got - want).abs(), want.abs()
-
-
-def _close(got, want, atol, rtol, what):
-    err, mag = _err(got, want)
-    worst = (err / (atol + rtol * mag)).max().item()
-    print(f"{what}: max err {err.max().item():.3e}, {worst:.3f} of the bound")
-    assert bool((err <= atol + rtol * mag).all()), f"{what}: max err {err.max().item():.3e} ({worst:.2f} x bound)"
-
-
-def _rel_close(got, want, tol, what):
-    err, mag = _err(got, want)
-    scale = mag.max().item() + 1e-12
-    print(f"{what}: max err {err.max().item():.3e} over scale {scale:.3e} = {err.max().item() / scale:.3e}")
-    assert err.max().item() <= tol * scale, f"{what}: max err {err.max().item():.3e} vs scale {scale:.3e}"
 
 
 def _golden_run(z, contract, name, geom, mask_dtype=None, mask_edit=None):
@@ -110,9 +72,9 @@ def test_attention_matches_reference_goldens(golden_dir, name):
         for got, k, atol in checks:
             assert got is not None, key + k
             if offset:
-                _rel_close(got, z[key + k], 1e-4, key + k)
+                rel_close(got, z[key + k], 1e-4, key + k)
             else:
-                _close(got, z[key + k], atol, 1e-4, key + k)
+                golden_ratio(got, z[key + k], atol, 1e-4, key + k)
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -222,7 +184,7 @@ def test_backward_without_a_weights_gradient(golden_dir):
             for k, got, want in ([(a, t.grad, t64.grad) for a, t, t64 in zip(ARGS[cls], inputs, in64)]
                                  + [(k, p.grad, p64[k].grad) for k, p in m.named_parameters()]):
                 assert got is not None and bool(torch.isfinite(got).all()), key + k
-                _close(got, want, 1e-5, 1e-4, key + "grad::" + k)
+                golden_ratio(got, want, 1e-5, 1e-4, key + "grad::" + k)
 
 
 # ----------------------------------------------------------------------------- the project's shapes
@@ -275,12 +237,12 @@ def test_project_shapes_against_float64(cls, shape):
     in64 = [t.double().requires_grad_(True) for t in raw]
     out64, weights64 = _module64(cls, p64, in64, mask)
     ((out64 * gout.double()).sum() + (weights64 * gweights.double()).sum()).backward()
-    _rel_close(o1, out64, 1e-4, "out")
-    _rel_close(w1, weights64, 1e-4, "weights")
+    rel_close(o1, out64, 1e-4, "out")
+    rel_close(w1, weights64, 1e-4, "weights")
     for k, got, t64 in zip(ARGS[cls], gi1, in64):
-        _rel_close(got, t64.grad, 1e-4, "grad::" + k)
+        rel_close(got, t64.grad, 1e-4, "grad::" + k)
     for k in gp1:
-        _rel_close(gp1[k], p64[k].grad, 1e-4, "grad::" + k)
+        rel_close(gp1[k], p64[k].grad, 1e-4, "grad::" + k)
 
 
 def test_sequences_beyond_the_documented_limits_are_rejected():
@@ -303,5 +265,5 @@ def test_sequences_beyond_the_documented_limits_are_rejected():
     left = torch.randn(2, 8, device=DEV)
     avg, w = dot(left, right, torch.ones(2, 4096, device=DEV))
     avg64, w64 = _query64(left.double(), right.double(), torch.ones(2, 4096, device=DEV))
-    _rel_close(avg, avg64, 1e-4, "avg after a rejected call")
-    _rel_close(w, w64, 1e-4, "weights after a rejected call")
+    rel_close(avg, avg64, 1e-4, "avg after a rejected call")
+    rel_close(w, w64, 1e-4, "weights after a rejected call")

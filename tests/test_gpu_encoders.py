@@ -1,14 +1,11 @@
 """GPU checks of the graph encoders GraphAttentionLayer / GAT / GCN (get_amd.modules, csrc/encoder_ops.hip) against the
 reference's captured outputs and gradients (tests/golden/g10_gat.npz, g11_gcn.npz), dense vs packed adjacency,
 replayed training-mode dropout through a float64 restatement, and the bench-scale graphs (960 x 100 nodes, width 300)."""
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
 
-from tests.util import _gat64, _gat_head64, _gcn64
+from tests.util import _gat64, _gat_head64, _gcn64, bits_equal, build_from_contract, golden_ratio, load_golden, rel_close
 
 pytestmark = pytest.mark.gpu
 
@@ -16,8 +13,7 @@ DEV = torch.device("cuda:0") if torch.cuda.is_available() else None
 
 
 def _load(golden_dir, name):
-    z = np.load(os.path.join(golden_dir, name))
-    return z, json.loads(bytes(z["meta"]).decode())
+    return load_golden(golden_dir, name, "encoder_contract.json")
 
 
 def _cases(z, meta, kinds):
@@ -27,37 +23,22 @@ def _cases(z, meta, kinds):
 
 
 def _build(z, key, contract):
-    from get_amd import modules
-    c = contract[key.split("/")[0]]
-    m = getattr(modules, c["class"])(**c["kwargs"])
-    sd = {k[len(key) + len("param::"):]: torch.from_numpy(z[k]) for k in z.files if k.startswith(key + "param::")}
-    m.load_state_dict(sd, strict=True)
-    return m.to(DEV).train(False)
-
-
-def _close(got, want, atol, rtol, what):
-    got = got.detach().double().cpu()
-    want = torch.as_tensor(np.asarray(want)).double()
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    err = (got - want).abs()
-    tol = atol + rtol * want.abs()
-    assert bool((err <= tol).all()), f"{what}: max err {err.max().item():.3e}"
+    return build_from_contract(z, key, contract[key.split("/")[0]]).to(DEV).train(False)
 
 
 def _run_golden(golden_dir, npz, kinds_key):
-    z, meta = _load(golden_dir, npz)
-    contract = json.load(open(os.path.join(golden_dir, "encoder_contract.json")))
+    z, meta, contract = _load(golden_dir, npz)
     n_cases = 0
     for name, kind, key in _cases(z, meta, meta[kinds_key]):
         m = _build(z, key, contract)
         x = torch.from_numpy(z[key + "x"]).to(DEV).requires_grad_(True)
         adj = torch.from_numpy(z[key + "adj"]).to(DEV)
         out = m(x, adj)
-        _close(out, z[key + "out"], 1e-4, 1e-4, key + "out")
+        golden_ratio(out, z[key + "out"], 1e-4, 1e-4, key + "out")
         (out * torch.from_numpy(z[key + "gout"]).to(DEV)).sum().backward()
-        _close(x.grad, z[key + "grad::x"], 1e-5, 1e-4, key + "grad::x")
+        golden_ratio(x.grad, z[key + "grad::x"], 1e-5, 1e-4, key + "grad::x")
         for k, p in m.named_parameters():
-            _close(p.grad, z[key + "grad::" + k], 1e-5, 1e-4, key + "grad::" + k)
+            golden_ratio(p.grad, z[key + "grad::" + k], 1e-5, 1e-4, key + "grad::" + k)
         n_cases += 1
     return n_cases
 
@@ -83,16 +64,15 @@ def _fwd_bwd(m, x, adj, gout):
 
 
 def _same(a, b):
-    oa, xa, pa = a
-    ob, xb, pb = b
-    assert torch.equal(oa, ob) and torch.equal(xa, xb)
-    assert all(torch.equal(u, v) for u, v in zip(pa, pb))
+    """Two (out, grad x, [parameter grads]) of _fwd_bwd: the same bits, none of them NaN."""
+    for i, (u, v) in enumerate(zip([a[0], a[1], *a[2]], [b[0], b[1], *b[2]])):
+        assert not bool(torch.isnan(u).any()), i
+        bits_equal(u, v, f"tensor {i} of two runs")
 
 
 def test_dense_and_packed_adjacency_are_bit_identical(golden_dir):
     from get_amd import ops
-    z, meta = _load(golden_dir, "g10_gat.npz")
-    contract = json.load(open(os.path.join(golden_dir, "encoder_contract.json")))
+    z, meta, contract = _load(golden_dir, "g10_gat.npz")
     for name in meta["gat_cases"]:
         key = f"{name}/text::"
         m = _build(z, key, contract)
@@ -111,7 +91,7 @@ def test_dense_and_packed_adjacency_are_bit_identical(golden_dir):
         _same(_fwd_bwd(m, x, dense, gout), _fwd_bwd(m, x, ops.PackedAdj.from_dense(dense), gout))
     # GCN: a dense tensor and its PackedAdj are the same operator; the native graph_build pattern (normalised mode)
     # gives the reference's result too
-    z, meta = _load(golden_dir, "g11_gcn.npz")
+    z, meta, contract = _load(golden_dir, "g11_gcn.npz")
     for name in meta["gcn_cases"]:
         key = f"{name}/text::"
         m = _build(z, key, contract)
@@ -122,8 +102,8 @@ def test_dense_and_packed_adjacency_are_bit_identical(golden_dir):
         packed, _, _ = ops.graph_build(torch.from_numpy(z[key + "tokens"]).to(DEV),
                                        torch.from_numpy(z[key + "lengths"]).to(DEV), meta["window"])
         out, gx, gp = _fwd_bwd(m, x, packed, gout)
-        _close(out, z[key + "out"], 1e-4, 1e-4, key + "packed out")
-        _close(gx, z[key + "grad::x"], 1e-5, 1e-4, key + "packed grad::x")
+        golden_ratio(out, z[key + "out"], 1e-4, 1e-4, key + "packed out")
+        golden_ratio(gx, z[key + "grad::x"], 1e-5, 1e-4, key + "packed grad::x")
 
 
 def _params64(m):
@@ -133,10 +113,10 @@ def _params64(m):
 def _check_grads(m, x_dev, gout, out_dev, x64, p64, out64, tol_out=1e-4, tol_g=1e-4):
     (out_dev * gout).sum().backward()
     (out64 * gout.double().cpu()).sum().backward()
-    _close(out_dev, out64.detach(), tol_out, tol_out, "out")
-    _close(x_dev.grad, x64.grad, tol_g, tol_g, "grad::x")
+    golden_ratio(out_dev, out64.detach(), tol_out, tol_out, "out")
+    golden_ratio(x_dev.grad, x64.grad, tol_g, tol_g, "grad::x")
     for k, p in m.named_parameters():
-        _close(p.grad, p64[k].grad, tol_g, tol_g, "grad::" + k)
+        golden_ratio(p.grad, p64[k].grad, tol_g, tol_g, "grad::" + k)
 
 
 def test_training_mode_dropout_replays(golden_dir):
@@ -198,14 +178,6 @@ def _bench_graphs():
     return packed
 
 
-def _rel_close(got, want, tol, what):
-    got = got.detach().double().cpu()
-    want = want.detach().double()
-    scale = want.abs().max().item() + 1e-12
-    err = (got - want).abs().max().item()
-    assert err <= tol * scale, f"{what}: max err {err:.3e} vs scale {scale:.3e}"
-
-
 def test_bench_scale_gat_and_gcn():
     """960 graphs x 100 nodes of gh_graph_build on synth tokens, width 300: GAT (3 heads, a hidden layer) and GCN
     forward + backward against float64 restatements; two runs bit-identical (no global atomics); no dense buffer.
@@ -245,10 +217,10 @@ def test_bench_scale_gat_and_gcn():
         else:
             y64 = _gcn64(p64, x64, adj64, 2, relu_masks=masks[:2])
         (y64 * gout.double().cpu()).sum().backward()
-        _rel_close(out, y64, 1e-4, "out")
-        _rel_close(gx, x64.grad, 1e-4, "grad::x")
+        rel_close(out, y64, 1e-4, "out")
+        rel_close(gx, x64.grad, 1e-4, "grad::x")
         for (k, _), g in zip(m.named_parameters(), gp):
-            _rel_close(g, p64[k].grad, 1e-4, "grad::" + k)
+            rel_close(g, p64[k].grad, 1e-4, "grad::" + k)
 
 
 def test_gat_memory_holds_no_attention_matrix():

@@ -2,62 +2,27 @@
 captured outputs and gradients (tests/golden/g14_lstm.npz), the padding conventions, the processing order, run-to-run
 determinism, the project's width against the float64 restatement of tests/lstm_ref.py, the replayed input dropout, the
 documented limits and the model's two encoders."""
-import json
-import os
-
-import numpy as np
 import pytest
 import torch
 
 from tests.lstm_ref import lstm64
+from tests.util import bits_equal, build_from_contract, golden_ratio, load_golden, rel_close
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0") if torch.cuda.is_available() else None
 
 CASES = ["bi_b5", "bi_b5_max25", "uni_h5", "two_layers", "bi_b37", "bi_l70", "bi_b5_saturated"]
-_GOLDEN = {}
 
 
 def _golden(golden_dir):
-    """The archive and the constructor contract, loaded once and never modified."""
-    if not _GOLDEN:
-        z = np.load(os.path.join(golden_dir, "g14_lstm.npz"))
-        _GOLDEN["z"] = {k: z[k] for k in z.files}
-        with open(os.path.join(golden_dir, "lstm_contract.json")) as fh:
-            _GOLDEN["contract"] = json.load(fh)
-    return _GOLDEN["z"], _GOLDEN["contract"]
-
-
-def _close(got, want, what, atol=1e-5, rtol=1e-4):
-    """|got - want| <= atol + rtol |want| elementwise; prints the achieved fraction of the bound."""
-    got = got.detach().double().cpu()
-    want = torch.as_tensor(np.asarray(want.detach().cpu() if torch.is_tensor(want) else want)).double()
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    assert bool(torch.isfinite(got).all()), what + ": not finite"
-    err = (got - want).abs()
-    worst = (err / (atol + rtol * want.abs())).max().item()
-    print(f"{what}: max err {err.max().item():.3e}, {worst:.3f} of the bound")
-    assert worst <= 1.0, f"{what}: max err {err.max().item():.3e} ({worst:.2f} x bound)"
-
-
-def _rel(got, want, what, tol=2e-5):
-    """max |got - want| <= tol max |want| per tensor (the project's float64 bound of its GEMM tests); prints the ratio."""
-    got = got.detach().double().cpu()
-    want = want.detach().double()
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    assert bool(torch.isfinite(got).all()), what + ": not finite"
-    err, scale = (got - want).abs().max().item(), want.abs().max().item()
-    print(f"{what}: max err {err:.3e} over max {scale:.3e} = {err / scale:.3e} ({err / scale / tol:.3f} of the bound {tol:.0e})")
-    assert err <= tol * scale, f"{what}: max err {err:.3e} vs max {scale:.3e}"
+    z, _, contract = load_golden(golden_dir, "g14_lstm.npz", "lstm_contract.json")
+    return z, contract
 
 
 def _module(z, contract, name):
     from get_amd import modules
-    key = f"{name}::param::"
-    m = modules.LSTM(**contract[name]["kwargs"])
-    m.load_state_dict({k[len(key):]: torch.from_numpy(z[k]) for k in z if k.startswith(key)}, strict=True)
-    return m.to(DEV).eval()
+    return build_from_contract(z, name + "::", contract[name], modules.LSTM).to(DEV).eval()
 
 
 def _pair(lens):
@@ -76,10 +41,6 @@ def _run(m, x, lens, pair, max_len, gy, gh, return_h=True):
     return y.detach(), h.detach(), grads
 
 
-def _bits_equal(a, b, what):
-    assert a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32)), what + " differs"
-
-
 @pytest.mark.parametrize("name", CASES)
 def test_lstm_matches_reference_goldens(golden_dir, name):
     """y, h and every gradient (x and all parameters) within 1e-5 + 1e-4 |want| of the reference's fp32 results, elementwise.
@@ -89,17 +50,17 @@ def test_lstm_matches_reference_goldens(golden_dir, name):
     g = lambda k: torch.from_numpy(z[f"{name}::{k}"])
     pair = (g("new_indices"), g("restoring_indices"))
     y, h, grads = _run(m, g("x"), g("lens"), pair, contract[name]["max_len"], g("gy"), g("gh"))
-    _close(y, g("y"), name + "::y")
-    _close(h, g("h"), name + "::h")
+    golden_ratio(y, g("y"), 1e-5, 1e-4, name + "::y")
+    golden_ratio(h, g("h"), 1e-5, 1e-4, name + "::h")
     assert set(grads) == {"x"} | {k for k, _ in contract[name]["state_dict"]}
     for k, got in grads.items():
         assert got is not None, k
-        _close(got, g("grad::" + k), f"{name}::grad::{k}")
+        golden_ratio(got, g("grad::" + k), 1e-5, 1e-4, f"{name}::grad::{k}")
     if name == "bi_b37":      # return_h=False: the raw (layers * dirs, B, H) state in the sorted order
         with torch.no_grad():
             y2, raw = m((g("x").to(DEV), g("lens"), pair[0], pair[1]), return_h=False)
-        _bits_equal(y2, y, "y of return_h=False")
-        _close(raw, g("h_raw"), name + "::h_raw")
+        bits_equal(y2, y, "y of return_h=False")
+        golden_ratio(raw, g("h_raw"), 1e-5, 1e-4, name + "::h_raw")
 
 
 def test_padding_never_reaches_a_result(golden_dir):
@@ -118,10 +79,10 @@ def test_padding_never_reaches_a_result(golden_dir):
     assert bool(dead.any()) and not torch.equal(x, x2)
     y, h, grads = _run(m, x, lens, pair, 25, g("gy"), g("gh"))
     y2, h2, grads2 = _run(m, x2, lens, pair, 25, g("gy"), g("gh"))
-    _bits_equal(y, y2, "y")
-    _bits_equal(h, h2, "h")
+    bits_equal(y, y2, "y")
+    bits_equal(h, h2, "h")
     for k in grads:
-        _bits_equal(grads[k], grads2[k], "grad " + k)
+        bits_equal(grads[k], grads2[k], "grad " + k)
     dead_t = torch.arange(25)[None, :] >= lens[:, None]
     assert y.shape == (5, 25, 16) and bool((y.cpu()[dead_t] == 0).all()) and bool((y[:, L:] == 0).all())
     assert bool((grads["x"].cpu()[dead] == 0).all())
@@ -131,7 +92,7 @@ def test_padding_never_reaches_a_result(golden_dir):
     y0, h0, grads0 = _run(m, x, lens0.to(DEV), _pair(lens0), 25, g("gy"), g("gh"))
     assert bool((y0[1] == 0).all()) and bool((h0[1] == 0).all()) and bool((grads0["x"][1] == 0).all())
     assert all(bool(torch.isfinite(v).all()) for v in grads0.values())
-    _bits_equal(y0[0], y[0], "an untouched sequence next to an empty one")
+    bits_equal(y0[0], y[0], "an untouched sequence next to an empty one")
     # host lengths outside [1, T] raise as the reference's pack / pad functions do
     with pytest.raises(ValueError):
         m((x.to(DEV), lens0, pair[0], pair[1]), max_len=25)
@@ -151,10 +112,10 @@ def test_processing_order_does_not_change_a_bit(golden_dir):
     lens = g("lens").to(DEV)          # on the device: no host check of the order
     y, h, grads = _run(m, g("x"), lens, (g("new_indices"), g("restoring_indices")), 20, g("gy"), g("gh"))
     y2, h2, grads2 = _run(m, g("x"), lens, ident, 20, g("gy"), g("gh"))
-    _bits_equal(y, y2, "y")
-    _bits_equal(h, h2, "h")
+    bits_equal(y, y2, "y")
+    bits_equal(h, h2, "h")
     for k in grads:
-        _bits_equal(grads[k], grads2[k], "grad " + k)
+        bits_equal(grads[k], grads2[k], "grad " + k)
 
 
 def test_two_runs_are_bit_identical(golden_dir):
@@ -165,13 +126,13 @@ def test_two_runs_are_bit_identical(golden_dir):
         args = (g("x"), g("lens"), (g("new_indices"), g("restoring_indices")), None, g("gy"), g("gh"))
         y, h, grads = _run(m, *args)
         y2, h2, grads2 = _run(m, *args)
-        _bits_equal(y, y2, "y")
-        _bits_equal(h, h2, "h")
+        bits_equal(y, y2, "y")
+        bits_equal(h, h2, "h")
         for k in grads:
-            _bits_equal(grads[k], grads2[k], "grad " + k)
+            bits_equal(grads[k], grads2[k], "grad " + k)
 
 
-def _against_float64(m, x, lens, T, seed, what, drop_mask=None, p=0.0, check=_rel):
+def _against_float64(m, x, lens, T, seed, what, drop_mask=None, p=0.0):
     gen = torch.Generator().manual_seed(seed)
     H, dirs, layers = m.rnn.hidden_size, 2 if m.rnn.bidirectional else 1, m.rnn.num_layers
     gy, gh = torch.randn(x.shape[0], T, dirs * H, generator=gen), torch.randn(x.shape[0], layers * dirs * H, generator=gen)
@@ -184,7 +145,7 @@ def _against_float64(m, x, lens, T, seed, what, drop_mask=None, p=0.0, check=_re
 
 def test_project_width_against_float64():
     """B=37, L=100, D=H=300, bidirectional, unsorted lengths including 1 and 100, against tests/lstm_ref.py in float64:
-    max |got - want| <= 2e-5 max |want| per tensor.  (An elementwise bound is not used at this shape: the reference's own fp32
+    max |got - want| <= 2e-5 max |want| per tensor (the project's float64 bound of its GEMM tests).  (An elementwise bound is not used at this shape: the reference's own fp32
     result misses 1e-5 + 1e-4 |want| on the weight_ih gradients there, through cancellation.)"""
     from get_amd import modules
     torch.manual_seed(11)
@@ -199,10 +160,10 @@ def test_project_width_against_float64():
     x = torch.randn(37, 100, 300, generator=gen)
     gy, gh, y64, h64, g64 = _against_float64(m, x, lens, 100, 13, "h300")
     y, h, grads = _run(m, x, lens, _pair(lens), 100, gy, gh)
-    _rel(y, y64, "h300 y")
-    _rel(h, h64, "h300 h")
+    rel_close(y, y64, 2e-5, "h300 y")
+    rel_close(h, h64, 2e-5, "h300 h")
     for k in grads:
-        _rel(grads[k], g64[k], "h300 grad " + k)
+        rel_close(grads[k], g64[k], 2e-5, "h300 grad " + k)
 
 
 def test_input_dropout_is_replayed_from_its_seed(golden_dir):
@@ -227,11 +188,11 @@ def test_input_dropout_is_replayed_from_its_seed(golden_dir):
     assert 0 < float(mask.mean()) < 1
     gy, gh, y64, h64, g64 = _against_float64(m, x, lens, 21, 17, "dropout", mask, p)
     ((y * gy.to(DEV)).sum() + (h * gh.to(DEV)).sum()).backward()
-    _close(y, y64, "dropout y")
-    _close(h, h64, "dropout h")
-    _close(xd.grad, g64["x"], "dropout grad x")
+    golden_ratio(y, y64, 1e-5, 1e-4, "dropout y")
+    golden_ratio(h, h64, 1e-5, 1e-4, "dropout h")
+    golden_ratio(xd.grad, g64["x"], 1e-5, 1e-4, "dropout grad x")
     for k, q in m.named_parameters():
-        _close(q.grad, g64[k], "dropout grad " + k)
+        golden_ratio(q.grad, g64[k], 1e-5, 1e-4, "dropout grad " + k)
 
 
 def test_limits_and_the_models_encoders():
@@ -251,10 +212,10 @@ def test_limits_and_the_models_encoders():
     x, lens = torch.randn(1, 3, 4, generator=gen), torch.tensor([3])
     gy, gh, y64, h64, g64 = _against_float64(m, x, lens, 3, 7, "h1024")
     y, h, grads = _run(m, x, lens, one, 3, gy, gh)
-    _rel(y, y64, "h1024 y")
-    _rel(h, h64, "h1024 h")
+    rel_close(y, y64, 2e-5, "h1024 y")
+    rel_close(h, h64, 2e-5, "h1024 h")
     for k in grads:
-        _rel(grads[k], g64[k], "h1024 grad " + k)
+        rel_close(grads[k], g64[k], 2e-5, "h1024 grad " + k)
     m = modules.LSTM(4, 4).to(DEV).eval()
     x, lens = torch.randn(1, 4096, 4, generator=gen), torch.tensor([4096])
     y, h, grads = _run(m, x, lens, one, 4096, torch.ones(1, 4096, 4), torch.ones(1, 4))

@@ -3,14 +3,11 @@ MultiHeadAttentionOriginal, ConcatNotEqualSelfAttTransFormer, MultiHeadAttention
 csrc/mha_ops.hip) against the reference's captured outputs and gradients (tests/golden/g13_mha.npz), the masking
 conventions, operands read in place from a wider tensor, run-to-run determinism, the project's word- and evidence-level
 shapes against the float64 restatements of tests/mha_ref.py, the LayerNorm alone, and the documented limits."""
-import json
-import os
-
-import numpy as np
 import pytest
 import torch
 
 from tests.mha_ref import layernorm64, module64
+from tests.util import build_from_contract, golden_ratio, load_golden, rel_close
 
 pytestmark = pytest.mark.gpu
 
@@ -19,56 +16,15 @@ DEV = torch.device("cuda:0") if torch.cuda.is_available() else None
 CASES = ["sdpa_3x5", "sdpa_35x70", "sdpa_offset_pos", "sdpa_offset_neg", "mha_orig_h3", "mha_orig_h1", "transformer_concat",
          "mha_simple_h3", "mha_simple_h3_ln"]
 
-_GOLDEN = {}
-
 
 def _golden(golden_dir):
-    """The archive, its meta and the constructor contract, loaded once and never modified."""
-    if not _GOLDEN:
-        z = np.load(os.path.join(golden_dir, "g13_mha.npz"))
-        _GOLDEN["z"] = {k: z[k] for k in z.files}
-        _GOLDEN["meta"] = json.loads(bytes(z["meta"]).decode())
-        with open(os.path.join(golden_dir, "mha_contract.json")) as fh:
-            _GOLDEN["contract"] = json.load(fh)
-    return _GOLDEN["z"], _GOLDEN["meta"], _GOLDEN["contract"]
-
-
-def _err(got, want):
-    got = got.detach().double().cpu()
-    want = torch.as_tensor(np.asarray(want.detach().cpu() if torch.is_tensor(want) else want)).double()
-    assert got.shape == want.shape, (got.shape, want.shape)
-    assert bool(torch.isfinite(got).all()), "not finite"
-    return (got - want).abs(), want.abs()
-
-
-def _close(got, want, atol, rtol, what):
-    err, mag = _err(got, want)
-    worst = (err / (atol + rtol * mag)).max().item()
-    print(f"{what}: max err {err.max().item():.3e}, {worst:.3f} of the bound")
-    assert bool((err <= atol + rtol * mag).all()), f"{what}: max err {err.max().item():.3e} ({worst:.2f} x bound)"
-
-
-def _rel_close(got, want, tol, what, floor=None):
-    """Largest error over largest entry of the float64 result.  `floor`: where that result is identically 0 because its terms
-    cancel, the size of the cancelling terms, which is what a rounding error is relative to (as tests/util.py _rel has it)."""
-    err, mag = _err(got, want)
-    scale = mag.max().item() + 1e-12
-    if floor is not None:
-        assert scale <= 1e-9 * float(floor), (what, scale, floor)      # only ever in place of a result that is identically 0
-        scale = float(floor)
-    print(f"{what}: max err {err.max().item():.3e} over scale {scale:.3e} = {err.max().item() / scale:.3e} (bound {tol:.0e})")
-    assert err.max().item() <= tol * scale, f"{what}: max err {err.max().item():.3e} vs scale {scale:.3e}"
+    return load_golden(golden_dir, "g13_mha.npz", "mha_contract.json")
 
 
 def _golden_run(z, meta, contract, name, geom, with_gweights=True):
     """Forward + backward of one golden case; returns (module, inputs by name, out, weights)."""
-    from get_amd import modules
     key = f"{name}/{geom}::"
-    c = contract[name]
-    m = getattr(modules, c["class"])(**c["kwargs"])
-    sd = {k[len(key) + len("param::"):]: torch.from_numpy(z[k]) for k in z if k.startswith(key + "param::")}
-    m.load_state_dict(sd, strict=True)
-    m = m.to(DEV)
+    m = build_from_contract(z, key, contract[name]).to(DEV)
     inputs = {a: torch.from_numpy(z[key + a]).to(DEV).requires_grad_(True) for a in dict.fromkeys(meta["args"][name])}
     out, weights = m(*[inputs[a] for a in meta["args"][name]], torch.from_numpy(z[key + "mask"]).to(DEV))
     loss = (out * torch.from_numpy(z[key + "gout"]).to(DEV)).sum()
@@ -97,9 +53,9 @@ def test_mha_matches_reference_goldens(golden_dir, name):
         for got, k, atol in checks:
             assert got is not None, key + k
             if offset:
-                _rel_close(got, z[key + k], 1e-4, key + k)
+                rel_close(got, z[key + k], 1e-4, key + k)
             else:
-                _close(got, z[key + k], atol, 1e-4, key + k)
+                golden_ratio(got, z[key + k], atol, 1e-4, key + k)
 
 
 @pytest.mark.parametrize("name", ["sdpa_3x5", "sdpa_35x70", "mha_orig_h3"])
@@ -209,11 +165,12 @@ def test_original_at_project_shapes_against_float64(shape):
     out, none = m(q, kv, kv, mask.to(DEV))
     assert none is None
     (out * gout.to(DEV)).sum().backward()
-    _rel_close(out, want, 1e-5, f"{shape} out")
-    _rel_close(q.grad, q64.grad, 1e-4, f"{shape} grad q")
-    _rel_close(kv.grad, kv64.grad, 1e-4, f"{shape} grad k=v")
+    rel_close(out, want, 1e-5, f"{shape} out")
+    rel_close(q.grad, q64.grad, 1e-4, f"{shape} grad q")
+    rel_close(kv.grad, kv64.grad, 1e-4, f"{shape} grad k=v")
     for k, p in m.named_parameters():
-        _rel_close(p.grad, p64[k].grad, 1e-4, f"{shape} grad {k}", floor=cancelling if k == "w_ks.bias" else None)
+        rel_close(p.grad, p64[k].grad, 1e-4, f"{shape} grad {k}", floor=cancelling if k == "w_ks.bias" else None,
+                  floor_replaces_zero=True)      # asserts that this float64 gradient is numerically zero before using floor
 
 
 @pytest.mark.parametrize("with_res", [False, True])
@@ -237,10 +194,10 @@ def test_add_layernorm_against_float64(d, with_res):
     y = ops.add_layernorm(x, r, w, bb, 1e-5)
     (y * gy.to(DEV)).sum().backward()
     what = f"layernorm d={d} res={with_res}"
-    _rel_close(y, want, 1e-5, what + " y")
-    _rel_close(x.grad, leaves64[0].grad, 1e-4, what + " dx")
-    _rel_close(w.grad, leaves64[1].grad, 1e-4, what + " dgamma")
-    _rel_close(bb.grad, leaves64[2].grad, 1e-4, what + " dbeta")
+    rel_close(y, want, 1e-5, what + " y")
+    rel_close(x.grad, leaves64[0].grad, 1e-4, what + " dx")
+    rel_close(w.grad, leaves64[1].grad, 1e-4, what + " dgamma")
+    rel_close(bb.grad, leaves64[2].grad, 1e-4, what + " dbeta")
     if with_res:
         assert torch.equal(r.grad, x.grad)
     # the kernel itself accumulates
@@ -321,7 +278,7 @@ def test_sizes_at_the_limits_run():
     q, k, v = (t.to(DEV).requires_grad_(True) for t in (q0, k0, v0))
     out, w = ops.mha_sdpa(q, k, v, mask.to(DEV), 1)
     (out * gout.to(DEV)).sum().backward()
-    _rel_close(out, want, 1e-5, "limits out")
-    _rel_close(w, w64, 1e-5, "limits weights")
+    rel_close(out, want, 1e-5, "limits out")
+    rel_close(w, w64, 1e-5, "limits weights")
     for a, c, n in zip((q, k, v), l64, "qkv"):
-        _rel_close(a.grad, c.grad, 1e-4, "limits grad " + n)
+        rel_close(a.grad, c.grad, 1e-4, "limits grad " + n)

@@ -2,7 +2,6 @@
 compare the kernels with (tests/lstm_ref.py) reproduces the reference's goldens on its own, the drop-in's constructor builds
 the reference's state_dict for every configuration in tests/golden/lstm_contract.json and initialises a stand-alone module
 as the reference does, the C-ABI declares and binds the two recurrence entries, and the module refuses CPU tensors."""
-import json
 import os
 import re
 
@@ -11,28 +10,26 @@ import pytest
 import torch
 
 from tests.lstm_ref import lstm64
-from tests.util import golden_ratio
+from tests.util import golden_ratio, load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = ["bi_b5", "bi_b5_max25", "uni_h5", "two_layers", "bi_b37", "bi_l70", "bi_b5_saturated"]
 
 
 def _archive(golden_dir):
-    z = np.load(os.path.join(golden_dir, "g14_lstm.npz"))
-    with open(os.path.join(golden_dir, "lstm_contract.json")) as fh:
-        return z, json.loads(bytes(z["meta"]).decode()), json.load(fh)
+    return load_golden(golden_dir, "g14_lstm.npz", "lstm_contract.json")
 
 
 def _params(z, name):
     key = f"{name}::param::"
-    return {k[len(key):]: torch.from_numpy(z[k]) for k in z.files if k.startswith(key)}
+    return {k[len(key):]: torch.from_numpy(z[k]) for k in z if k.startswith(key)}
 
 
 def test_lstm_golden_archive_is_complete(golden_dir):
     z, meta, contract = _archive(golden_dir)
     assert meta["cases"] == CASES and set(contract) == set(CASES)
     for name in CASES:
-        have = {k[len(name) + 2:] for k in z.files if k.startswith(name + "::")}
+        have = {k[len(name) + 2:] for k in z if k.startswith(name + "::")}
         assert {"x", "lens", "new_indices", "restoring_indices", "y", "h", "gy", "gh", "grad::x"} <= have, name
         names = [k for k, _ in contract[name]["state_dict"]]
         assert {k[len("param::"):] for k in have if k.startswith("param::")} == set(names)
@@ -47,7 +44,7 @@ def test_lstm_golden_archive_is_complete(golden_dir):
     assert list(z["bi_b5::lens"]) == [21, 9, 9, 1, 14] and z["bi_b5_max25::y"].shape == (5, 25, 16)
     assert (z["bi_b5_max25::y"][:, 21:] == 0).all()
     assert np.array_equal(z["bi_b5_saturated::x"], np.float32(30.0) * z["bi_b5::x"])
-    assert "bi_b37::h_raw" in z.files and z["bi_b37::h_raw"].shape == (2, 37, 12)
+    assert "bi_b37::h_raw" in z and z["bi_b37::h_raw"].shape == (2, 37, 12)
     assert os.path.getsize(os.path.join(golden_dir, "g14_lstm.npz")) < 300 * 1024
 
 

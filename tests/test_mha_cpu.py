@@ -4,19 +4,14 @@ CoDaAttention): the install() shim exports them, their constructors build the re
 configuration in tests/golden/mha_contract.json, the golden archive g13_mha.npz is complete, the modules refuse CPU
 tensors, and the float64 restatements the GPU tests compare the kernels with (tests/mha_ref.py) reproduce the archive on
 their own while keeping the exact-zero conventions."""
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 from tests.mha_ref import module64, sdpa64
-from tests.util import golden_ratio
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.util import golden_ratio, load_golden, rel_close, run_in_fresh_interpreter
 
 CASES = {"sdpa_3x5": {"n2q3k5": [2, 3, 5]}, "sdpa_35x70": {"n2q35k70": [2, 35, 70]},
          "sdpa_offset_pos": {"n2q3k12": [2, 3, 12]}, "sdpa_offset_neg": {"n2q3k12": [2, 3, 12]},
@@ -29,20 +24,11 @@ NO_WEIGHTS = ("mha_orig_h3", "mha_orig_h1")
 
 
 def _archive(golden_dir):
-    z = np.load(os.path.join(golden_dir, "g13_mha.npz"))
-    with open(os.path.join(golden_dir, "mha_contract.json")) as fh:
-        return z, json.loads(bytes(z["meta"]).decode()), json.load(fh)
+    return load_golden(golden_dir, "g13_mha.npz", "mha_contract.json")
 
 
 def test_install_shim_exports_the_multi_head_family(tmp_path):
-    os.makedirs(os.path.join(tmp_path, "thirdparty"), exist_ok=True)
-    open(os.path.join(tmp_path, "thirdparty", "__init__.py"), "w").close()
-    code = r"""
-import sys
-sys.path.insert(0, %r)
-sys.path.insert(0, %r)
-import get_amd
-M = get_amd.install()
+    run_in_fresh_interpreter(tmp_path, r"""
 from thirdparty.two_branches_attention import *
 from get_amd import modules
 assert ScaledDotProductAttention is modules.ScaledDotProductAttention
@@ -51,10 +37,7 @@ assert ConcatNotEqualSelfAttTransFormer is modules.ConcatNotEqualSelfAttTransFor
 assert MultiHeadAttentionSimple is modules.MultiHeadAttentionSimple
 assert CoDaAttention is modules.CoDaAttention
 assert CoDaAttention(4)(1, 2) is None and not list(CoDaAttention(4).parameters())
-print('ok')
-""" % (ROOT, str(tmp_path))
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stderr[-2000:]
+""")
 
 
 def test_mha_state_dicts_match_the_reference_contract(golden_dir):
@@ -87,7 +70,7 @@ def test_mha_golden_archive_is_complete(golden_dir):
     for name, geoms in CASES.items():
         for geom, dims in geoms.items():
             key = f"{name}/{geom}::"
-            have = {k[len(key):] for k in z.files if k.startswith(key)}
+            have = {k[len(key):] for k in z if k.startswith(key)}
             assert {"mask", "out", "gout"} <= have, key
             if name in NO_WEIGHTS:
                 assert "weights" not in have
@@ -109,7 +92,7 @@ def test_mha_golden_archive_is_complete(golden_dir):
                 assert list(mask.shape) == dims and (mask != 0).any(-1).all()
     single = ~z["sdpa_3x5/n2q3k5::mask"]
     assert (single.sum(-1) == 1).any()
-    for k in z.files:
+    for k in z:
         if k != "meta":
             assert np.isfinite(z[k]).all(), k
     assert os.path.getsize(os.path.join(golden_dir, "g13_mha.npz")) < 1 << 20
@@ -150,7 +133,7 @@ def _run64(z, meta, contract, name, geom):
     key = f"{name}/{geom}::"
     c = contract[name]
     p64 = {k[len(key) + len("param::"):]: torch.from_numpy(z[k]).double().requires_grad_(True)
-           for k in z.files if k.startswith(key + "param::")}
+           for k in z if k.startswith(key + "param::")}
     in64 = {a: torch.from_numpy(z[key + a]).double().requires_grad_(True) for a in dict.fromkeys(meta["args"][name])}
     out, weights = module64(c["class"], c["kwargs"], p64, [in64[a] for a in meta["args"][name]], torch.from_numpy(z[key + "mask"]))
     loss = (out * torch.from_numpy(z[key + "gout"]).double()).sum()
@@ -174,13 +157,11 @@ def test_float64_restatements_reproduce_the_mha_goldens(golden_dir):
             checks += [("grad::" + k, t.grad, 1e-5) for k, t in p64.items()]
             for k, got, atol in checks:
                 if name in meta["offset_cases"]:
-                    want = torch.from_numpy(z[key + k]).double()
-                    rel = ((got.detach() - want).abs().max() / (want.abs().max() + 1e-12)).item()
-                    assert rel <= 1e-4, (key + k, rel)
+                    rel_close(got, z[key + k], 1e-4, key + k)
                 else:
                     worst = max(worst, golden_ratio(got, z[key + k], atol, 1e-4, key + k))
                 checked.add(key + k)
-    recorded = {k for k in z.files if k.split("::", 1)[-1].split("::")[0] in ("out", "weights", "grad")}
+    recorded = {k for k in z if k.split("::", 1)[-1].split("::")[0] in ("out", "weights", "grad")}
     assert checked == recorded, sorted(recorded ^ checked)
     print(f"g13_mha.npz: worst ratio of the bound {worst:.3f}")
 

@@ -1,6 +1,8 @@
 """Shared helpers for the parity tests (fixtures, gradient summaries, tolerances)."""
 import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 import torch
@@ -50,45 +52,112 @@ def dense_from_coo(z, idx, fixed_length):
     return a
 
 
-def golden_ratio(got, want, atol, rtol, what):
-    """Assert |got - want| <= atol + rtol |want| elementwise (the golden tests' bound); returns the worst ratio of it."""
-    got = torch.as_tensor(np.asarray(got.detach().cpu() if torch.is_tensor(got) else got)).double()
-    want = torch.as_tensor(np.asarray(want)).double()
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    err = (got - want).abs()
-    tol = atol + rtol * want.abs()
-    worst = (err / tol).max().item()
-    assert bool(torch.isfinite(got).all()) and bool((err <= tol).all()), \
-        f"{what}: max err {err.max().item():.3e} ({worst:.2f} x bound)"
-    return worst
-
-
-# ----------------------------------------------------------------------------- path-by-path parity (tests/test_gpu_*_paths.py)
+# ----------------------------------------------------------------------------- comparisons (every parity and golden test)
 TOL = 1e-4                       # of the largest entry of the float64 result (the project's bound for restatements)
 WORST = {}                       # family -> worst observed err / scale, printed with every case (DESIGN.md 4.6, 4.7)
 
 
-def _rel(got, want, what, fam, floor=None):
-    """Finite and max error <= TOL of the float64 result's largest entry; prints and records the ratio.  `floor`: where
-    the float64 result is identically 0 because its terms cancel (the softmax over a single element has a zero
-    Jacobian), the size of the cancelling terms, which is what a rounding error is relative to."""
-    got = got.detach().double().cpu()
-    want = want.detach().double()
+def _f64(t):
+    """A tensor on any device, or anything numpy can read, as a float64 CPU tensor."""
+    return t.detach().double().cpu() if torch.is_tensor(t) else torch.as_tensor(np.asarray(t)).double()
+
+
+def golden_ratio(got, want, atol, rtol, what):
+    """Equal shapes, `got` finite and |got - want| <= atol + rtol |want| elementwise (the golden tests' bound); prints and
+    returns the worst fraction of that bound."""
+    got, want = _f64(got), _f64(want)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    assert bool(torch.isfinite(got).all()), f"{what}: {int((~torch.isfinite(got)).sum())} elements not written / not finite"
+    err = (got - want).abs()
+    tol = atol + rtol * want.abs()
+    worst = (err / tol).max().item()
+    print(f"{what}: max err {err.max().item():.3e}, {worst:.3f} of the bound")
+    assert bool((err <= tol).all()), f"{what}: max err {err.max().item():.3e} ({worst:.2f} x bound)"
+    return worst
+
+
+def rel_close(got, want, tol, what, floor=None, fam=None, floor_replaces_zero=False):
+    """Equal shapes, `got` finite and max |got - want| <= tol * scale, scale = max |want| + 1e-12; prints the ratio and, with
+    `fam`, records it in WORST[fam].  `floor`: where the float64 result is identically 0 because its terms cancel (the
+    softmax over a single element has a zero Jacobian), the size of the cancelling terms, which is what a rounding error is
+    relative to.  It replaces the scale only where the scale is <= 1e-12, and is ignored otherwise; a caller that knows the
+    result to be a cancellation passes floor_replaces_zero=True, which ASSERTS scale <= 1e-9 floor and then uses floor."""
+    got, want = _f64(got), _f64(want)
     assert got.shape == want.shape, (what, got.shape, want.shape)
     assert bool(torch.isfinite(got).all()), f"{what}: {int((~torch.isfinite(got)).sum())} elements not written / not finite"
     scale = want.abs().max().item() + 1e-12
-    if floor is not None and scale <= 1e-12:      # only ever in place of a result that is identically 0
+    if floor is not None and floor_replaces_zero:
+        assert scale <= 1e-9 * float(floor), (what, scale, floor)
+        scale = float(floor)
+    elif floor is not None and scale <= 1e-12:
         scale = float(floor)
     err = (got - want).abs().max().item()
-    WORST[fam] = max(WORST.get(fam, 0.0), err / scale)
-    print(f"{what}: max err {err:.3e} over scale {scale:.3e} = {err / scale:.3e} (worst {fam}: {WORST[fam]:.3e})")
-    assert err <= TOL * scale, f"{what}: max err {err:.3e} vs scale {scale:.3e}"
+    note = ""
+    if fam is not None:
+        WORST[fam] = max(WORST.get(fam, 0.0), err / scale)
+        note = f" (worst {fam}: {WORST[fam]:.3e})"
+    print(f"{what}: max err {err:.3e} over scale {scale:.3e} = {err / scale:.3e}, {err / scale / tol:.3f} of the bound {tol:.0e}{note}")
+    assert err <= tol * scale, f"{what}: max err {err:.3e} vs scale {scale:.3e}"
+    return err / scale
+
+
+def _rel(got, want, what, fam, floor=None):
+    """rel_close at the path tests' bound TOL, recorded under `fam` (tests/test_gpu_*_paths.py)."""
+    rel_close(got, want, TOL, what, floor=floor, fam=fam)
+
+
+def bits_equal(a, b, what):
+    """Same shape and the same 32-bit patterns: tells +0.0 from -0.0 and accepts equal NaN patterns."""
+    assert a.shape == b.shape, (what, a.shape, b.shape)
+    assert torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32)), what + " differs"
 
 
 def _same(a, b, what):
     for i, (u, v) in enumerate(zip(a, b)):
         if u is not None:
-            assert torch.equal(u.view(torch.int32), v.view(torch.int32)), f"{what}: output {i} differs between two calls"
+            bits_equal(u, v, f"{what}: output {i} of two calls")
+
+
+# ----------------------------------------------------------------------------- golden fixtures
+_LOADED = {}
+
+
+def load_golden(golden_dir, npz_name, contract_name=None):
+    """(archive as a dict of arrays, its decoded meta or None, the contract or None), read once per file and shared by every
+    test that asks again: nobody writes into what this returns."""
+    key = (golden_dir, npz_name, contract_name)
+    if key not in _LOADED:
+        with np.load(os.path.join(golden_dir, npz_name)) as f:
+            z = {k: f[k] for k in f.files}
+        meta = json.loads(bytes(z["meta"]).decode()) if "meta" in z else None
+        contract = None
+        if contract_name is not None:
+            with open(os.path.join(golden_dir, contract_name)) as fh:
+                contract = json.load(fh)
+        _LOADED[key] = (z, meta, contract)
+    return _LOADED[key]
+
+
+def build_from_contract(z, key_prefix, contract_entry, module_cls=None):
+    """The get_amd.modules class of a contract entry ("class", or `module_cls` where the contract names none) built from its
+    "kwargs", with every key_prefix + "param::*" array of the archive loaded into it (strict)."""
+    from get_amd import modules
+    m = (module_cls or getattr(modules, contract_entry["class"]))(**contract_entry["kwargs"])
+    pre = key_prefix + "param::"
+    m.load_state_dict({k[len(pre):]: torch.from_numpy(z[k]) for k in z if k.startswith(pre)}, strict=True)
+    return m
+
+
+def run_in_fresh_interpreter(tmp_path, body, packages=("thirdparty",)):
+    """get_amd.install() in a new interpreter that finds empty `packages` under tmp_path, followed by `body` (the imports
+    from the reference's module paths and the assertions on what they give)."""
+    for pkg in packages:
+        os.makedirs(os.path.join(tmp_path, pkg), exist_ok=True)
+        open(os.path.join(tmp_path, pkg, "__init__.py"), "w").close()
+    code = "import sys\nsys.path.insert(0, %r)\nsys.path.insert(0, %r)\nimport get_amd\nM = get_amd.install()\n%s\nprint('ok')\n" % (
+        ROOT, str(tmp_path), body)
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stderr[-2000:]
 
 
 # ----------------------------------------------------------------------------- float64 restatements (tests only)

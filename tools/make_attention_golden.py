@@ -25,23 +25,14 @@ test applies (tests/test_gpu_attention.py), so the fixture never eats the test's
 
     python tools/make_attention_golden.py
 """
-import importlib.util
-import io
 import json
 import os
-import sys
-import zipfile
 import zlib
 
 import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from oracle import _refshim  # noqa: E402
-
-import torch  # noqa: E402
-
-OUT = os.environ.get("GET_GOLDEN_OUT") or os.path.join(ROOT, "tests", "golden")
+from golden_common import OUT, load_reference, margin, to_numpy, write_contract, write_npz
 
 GEOMETRIES = {"b3l12": (3, 12), "b2l70": (2, 70)}
 D, X = 8, 5
@@ -62,16 +53,6 @@ CASES = {
 OFFSET_CASES = ("dot_offset_pos", "dot_offset_neg")
 # the GPU test's tolerances (elementwise atol + rtol |want|; offset cases: largest error over largest entry)
 TOL_OUT, TOL_GRAD, TOL_REL = (1e-4, 1e-4), (1e-5, 1e-4), 1e-4
-
-
-def load_reference(fname, modname):
-    path = os.path.join(_refshim.REF, "thirdparty", fname)
-    if not os.path.exists(path):
-        raise RuntimeError(f"reference not found at {path}")
-    spec = importlib.util.spec_from_file_location(modname, path)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def make_mask(b, l):
@@ -131,47 +112,30 @@ def run(ref, spec, name, geom, dtype):
     for k, p in m.named_parameters():
         res["param::" + k] = p
         res["grad::" + k] = p.grad
-    res = {k: (v.detach().numpy().copy() if torch.is_tensor(v) else v) for k, v in res.items()}
-    return m, res
+    return m, to_numpy(res)
 
 
-def check_margin(name, geom, r32, r64):
-    """The reference's fp32 result against its float64 one: within a tenth of the GPU test's tolerance."""
-    for k, got in r32.items():
-        if not (k in ("out", "weights") or k.startswith("grad::")):
-            continue
-        want = r64[k].astype(np.float64)
-        err = np.abs(got.astype(np.float64) - want)
+def margin_of(name, r32, r64):
+    """The reference's fp32 result against its float64 one, as a fraction of a tenth of the GPU test's tolerance."""
+    def bound(k, want):
         if name in OFFSET_CASES:
-            rel = err.max() / (np.abs(want).max() + 1e-12)
-            assert rel <= 0.1 * TOL_REL, (name, geom, k, rel)
-        else:
-            atol, rtol = TOL_OUT if k in ("out", "weights") else TOL_GRAD
-            assert (err <= 0.1 * (atol + rtol * np.abs(want))).all(), (name, geom, k, err.max())
-
-
-def write_npz(path, arrays):
-    """np.load-compatible archive with fixed member timestamps, so that a rerun reproduces the file byte for byte."""
-    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as zf:
-        for k in sorted(arrays):
-            buf = io.BytesIO()
-            np.lib.format.write_array(buf, np.ascontiguousarray(arrays[k]), allow_pickle=False)
-            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
-            info.compress_type = zipfile.ZIP_DEFLATED
-            info.external_attr = 0o644 << 16
-            zf.writestr(info, buf.getvalue())
+            return TOL_REL * (np.abs(want).max() + 1e-12)
+        atol, rtol = TOL_OUT if k in ("out", "weights") else TOL_GRAD
+        return atol + rtol * np.abs(want)
+    return margin(r32, r64, [k for k in r32 if k in ("out", "weights") or k.startswith("grad::")], bound)
 
 
 def main():
-    ref = {"two": load_reference("two_branches_attention.py", "ref_two_branches_attention"),
-           "self": load_reference("self_attention.py", "ref_self_attention")}
+    ref = {"two": load_reference("thirdparty/two_branches_attention.py", "ref_two_branches_attention"),
+           "self": load_reference("thirdparty/self_attention.py", "ref_self_attention")}
     torch.set_num_threads(1)
     store, contract = {}, {}
     for name, spec in CASES.items():
         for geom in GEOMETRIES:
             m, r32 = run(ref, spec, name, geom, torch.float32)
             _, r64 = run(ref, spec, name, geom, torch.float64)
-            check_margin(name, geom, r32, r64)
+            worst = margin_of(name, r32, r64)
+            assert worst <= 1.0, (name, geom, worst)
             contract.setdefault(name, {"class": spec["cls"], "kwargs": spec["kw"],
                                        "state_dict": [[k, list(v.shape)] for k, v in m.state_dict().items()]})
             for k, v in r32.items():
@@ -179,9 +143,7 @@ def main():
     meta = {"cases": list(CASES), "geometries": {k: list(v) for k, v in GEOMETRIES.items()}, "offset_cases": list(OFFSET_CASES)}
     store["meta"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
     write_npz(os.path.join(OUT, "g12_attention.npz"), store)
-    with open(os.path.join(OUT, "attention_contract.json"), "w") as fh:
-        json.dump(contract, fh, indent=1, sort_keys=True)
-        fh.write("\n")
+    write_contract(os.path.join(OUT, "attention_contract.json"), contract)
     for f in ("g12_attention.npz", "attention_contract.json"):
         print(f, os.path.getsize(os.path.join(OUT, f)), "bytes")
 

@@ -15,22 +15,15 @@ parameter (``grad::<name>``) and of x (``grad::x``).
 
     python tools/make_encoder_golden.py
 """
-import importlib.util
 import json
 import os
-import sys
 import zlib
 
 import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from oracle import _refshim  # noqa: E402
-from oracle.get_oracle import convert_text  # noqa: E402
-
-import torch  # noqa: E402
-
-OUT = os.environ.get("GET_GOLDEN_OUT") or os.path.join(ROOT, "tests", "golden")
+from golden_common import OUT, load_reference, write_contract      # puts the repository root on sys.path
+from oracle.get_oracle import convert_text
 
 # shapes: B graphs of L nodes; tokens shorter than L leave padding nodes (no edges: uniform attention rows)
 B, L, WINDOW = 3, 12, 3
@@ -47,16 +40,6 @@ GCN_CASES = {
     "gcn_l2": dict(cls="GCN", kw=dict(input_dim=8, hidden_dim=6, output_dim=6, num_layers=2)),
 }
 ADJ_KINDS = ("text", "weighted")
-
-
-def load_reference_wrapper():
-    path = os.path.join(_refshim.REF, "Models", "BiDAF", "wrapper.py")
-    if not os.path.exists(path):
-        raise RuntimeError(f"reference not found at {path}")
-    spec = importlib.util.spec_from_file_location("ref_bidaf_wrapper", path)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def text_graphs(rng):
@@ -112,7 +95,7 @@ def run_case(ref, store, contract, name, spec, kind, adj_np, tokens=None, length
 
 
 def main():
-    ref = load_reference_wrapper()
+    ref = load_reference("Models/BiDAF/wrapper.py", "ref_bidaf_wrapper")
     torch.set_num_threads(4)
     rng = np.random.default_rng(20241016)
     tokens, lengths, text_adj = text_graphs(rng)
@@ -133,9 +116,7 @@ def main():
     enc = lambda d: np.frombuffer(json.dumps(d).encode(), dtype=np.uint8)
     np.savez_compressed(os.path.join(OUT, "g10_gat.npz"), meta=enc(meta), **gat)
     np.savez_compressed(os.path.join(OUT, "g11_gcn.npz"), meta=enc(meta), **gcn)
-    with open(os.path.join(OUT, "encoder_contract.json"), "w") as fh:
-        json.dump(contract, fh, indent=1, sort_keys=True)
-        fh.write("\n")
+    write_contract(os.path.join(OUT, "encoder_contract.json"), contract)
     for f in ("g10_gat.npz", "g11_gcn.npz", "encoder_contract.json"):
         print(f, os.path.getsize(os.path.join(OUT, f)), "bytes")
 

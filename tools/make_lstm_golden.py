@@ -31,23 +31,14 @@ for all tensors.
 
     python tools/make_lstm_golden.py
 """
-import importlib.util
-import io
 import json
 import os
-import sys
-import zipfile
 import zlib
 
 import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from oracle import _refshim  # noqa: E402
-
-import torch  # noqa: E402
-
-OUT = os.environ.get("GET_GOLDEN_OUT") or os.path.join(ROOT, "tests", "golden")
+from golden_common import OUT, load_reference, margin, to_numpy, write_contract, write_npz
 
 B37_LENS = [7, 20, 3, 12, 1, 16, 9, 9, 20, 5, 14, 2, 18, 11, 6, 20, 4, 13, 8, 17, 10, 1, 15, 19, 3, 12, 7, 20, 6, 9, 2, 16, 11, 5, 14, 8,
             13]
@@ -62,16 +53,6 @@ CASES = {
     "bi_b5_saturated": dict(BI_B5, max_len=None, scale=30.0, seed_as="bi_b5"),
 }
 TOL = (1e-5, 1e-4)      # the tests' bound: atol + rtol |want|, elementwise, outputs and gradients alike
-
-
-def load_reference():
-    path = os.path.join(_refshim.REF, "Models", "BiDAF", "wrapper.py")
-    if not os.path.exists(path):
-        raise RuntimeError(f"reference not found at {path}")
-    spec = importlib.util.spec_from_file_location("ref_bidaf_wrapper", path)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def run(ref, name, spec, dtype):
@@ -102,46 +83,27 @@ def run(ref, name, spec, dtype):
     if spec.get("raw"):
         with torch.no_grad():
             res["h_raw"] = m((x, lens, new, restoring), return_h=False, max_len=spec["max_len"])[1]
-    res = {k: (v.detach().numpy().copy() if torch.is_tensor(v) else v) for k, v in res.items()}
-    return m, res
+    return m, to_numpy(res)
 
 
-def margin(r32, r64, skip=()):
-    """The reference's fp32 result against its float64 one, as a fraction of a tenth of the tests' bound."""
-    worst = 0.0
-    for k, got in r32.items():
-        if (k in ("y", "h", "h_raw") or k.startswith("grad::")) and k not in skip:
-            want = r64[k].astype(np.float64)
-            err = np.abs(got.astype(np.float64) - want)
-            worst = max(worst, (err / (0.1 * (TOL[0] + TOL[1] * np.abs(want)))).max())
-    return worst
-
-
-def write_npz(path, arrays):
-    """np.load-compatible archive with fixed member timestamps, so that a rerun reproduces the file byte for byte."""
-    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as zf:
-        for k in sorted(arrays):
-            buf = io.BytesIO()
-            np.lib.format.write_array(buf, np.ascontiguousarray(arrays[k]), allow_pickle=False)
-            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
-            info.compress_type = zipfile.ZIP_DEFLATED
-            info.external_attr = 0o644 << 16
-            zf.writestr(info, buf.getvalue())
+def bound(k, want):
+    return TOL[0] + TOL[1] * np.abs(want)
 
 
 def main():
-    ref = load_reference()
+    ref = load_reference("Models/BiDAF/wrapper.py", "ref_bidaf_wrapper")
     torch.set_num_threads(1)
     store, contract = {}, {}
     for name, spec in CASES.items():
         m, r32 = run(ref, name, spec, torch.float32)
         _, r64 = run(ref, name, spec, torch.float64)
         cancelling = [k for k in r32 if k.startswith("grad::rnn.weight_ih")] if name == "bi_b5_saturated" else []
-        worst = margin(r32, r64, skip=cancelling)
+        checked = [k for k in r32 if k in ("y", "h", "h_raw") or k.startswith("grad::")]
+        worst = margin(r32, r64, [k for k in checked if k not in cancelling], bound)
         print(f"{name}: fp32 reference at {worst:.3f} of a tenth of the bound")
         assert worst <= 1.0, (name, worst)
         if cancelling:
-            w = 0.1 * margin({k: r32[k] for k in cancelling}, r64)
+            w = 0.1 * margin(r32, r64, cancelling, bound)
             print(f"{name}: weight_ih gradients (cancelling sums over 30-fold inputs): fp32 reference at {w:.3f} of the bound")
             assert w <= 0.6, (name, w)
         assert all(np.isfinite(v).all() for v in r32.values())
@@ -151,9 +113,7 @@ def main():
             store[f"{name}::{k}"] = v
     store["meta"] = np.frombuffer(json.dumps({"cases": list(CASES)}).encode(), dtype=np.uint8)
     write_npz(os.path.join(OUT, "g14_lstm.npz"), store)
-    with open(os.path.join(OUT, "lstm_contract.json"), "w") as fh:
-        json.dump(contract, fh, indent=1, sort_keys=True)
-        fh.write("\n")
+    write_contract(os.path.join(OUT, "lstm_contract.json"), contract)
     for f in ("g14_lstm.npz", "lstm_contract.json"):
         print(f, os.path.getsize(os.path.join(OUT, f)), "bytes")
     assert os.path.getsize(os.path.join(OUT, "g14_lstm.npz")) < 300 * 1024
