@@ -36,4 +36,7 @@ def install():
     # the model itself (master_get.py:5,145)
     _module("Models.FCWithEvidences.graph_based_semantic_structure",
             Graph_basedSemantiStructure=M.Graph_basedSemantiStructure, KeyWordSettings=KeyWordSettings)
+    # the sequence-matching baseline built from wrapper.LSTM / wrapper.Linear
+    _module("Models.BiDAF.bidaf_model", BiDAF=M.BiDAF, LSTM=M.LSTM, Linear=M.Linear, KeyWordSettings=KeyWordSettings,
+            torch=torch, nn=nn, np=np)
     return M

@@ -12,6 +12,7 @@ load unchanged:
   thirdparty/self_attention.py                 MultiHeadSelfAttentionICLR2017Extend, SelfAttentionICLR2017,
                                                MultiHeadSelfAttentionICLR17OnWord, SelfAttentionType
   Models/FCWithEvidences/graph_based_semantic_structure.py   Graph_basedSemantiStructure
+  Models/BiDAF/bidaf_model.py                  BiDAF
 
 Adjacency arguments may be the reference's dense ``(N,R,R)`` tensors (any float dtype; packed once
 on the device, values kept exactly) or a native :class:`get_amd.ops.PackedAdj` from
@@ -901,3 +902,83 @@ class Graph_basedSemantiStructure(nn.Module):
     def _pad_right_tensor(cls, tsr: torch.Tensor, **kargs):
         cnt = kargs[KeyWordSettings.EvidenceCountPerQuery]
         return ops.seg_pad(tsr, ops.Segments(cnt, tsr.size(0), kargs[KeyWordSettings.FIXED_NUM_EVIDENCES]))
+
+
+# ------------------------------------------------------------------ Models/BiDAF/bidaf_model.py:11-172
+class BiDAF(nn.Module):
+    """The reference's BiDAF sequence-matching baseline on the HIP kernels: the highway gate and the attention-flow layer of
+    csrc/bidaf_ops.hip (ops.highway, ops.att_flow), the LSTM drop-in for the two encoders, ops.linear for every projection.
+
+    params keys read (the reference's, no others): ``embedding`` (a numpy matrix) or ``embedding_input_dim`` /
+    ``embedding_output_dim``, ``embedding_freeze``, ``word_dim``, ``hidden_size``, ``dropout``; the two dims are written back
+    into params when a matrix is given, as BaseModel._make_default_embedding_layer does.  Submodule names, order, shapes and
+    inits are the reference's, so state_dict() matches key for key.  The nn.Sequential(Linear, ReLU | Sigmoid) holders of the
+    highway layers only keep those keys: the forward calls their Linear and folds the activation into ops.highway.
+
+    forward(query (B,L) ids, document (B,R) ids, query_lens_indices=(new_indices, restoring_indices, lens),
+    doc_lens_indices=(...)) -> (B, 1).  Both sides are encoded to max(lens) steps, as pad_packed_sequence leaves them.
+    The attention-flow layer has NO mask, as in the reference: the encoder's exact-zero rows at t >= len take part in both
+    softmaxes.  Where the reference's .squeeze() calls break it -- B == 1 raises there, a context of length 1 broadcasts to a
+    wrong shape -- this class computes the layer's formulas (ops.att_flow); it emulates neither.  The gradients of the three
+    attention biases are mathematically zero and arrive as exact zeros.  Limits (ops.att_flow): context and query length <=
+    1024, hidden_size <= 1024.
+    Training mode: the only dropout sites are the input dropouts of the three LSTM calls; their seeds are kept in
+    ``last_seeds`` (context encoder on the document, context encoder on the query, modeling encoder), since the second call
+    of ``context_LSTM`` overwrites its ``last_seed``."""
+
+    def __init__(self, params):
+        super().__init__()
+        _drop_caches_on_load(self)
+        self._params = params
+        self.word_emb = Graph_basedSemantiStructure._make_default_embedding_layer(params)
+        D, H = params["word_dim"], params["hidden_size"]
+        for i in range(2):
+            setattr(self, "highway_linear%s" % i, nn.Sequential(Linear(D, D), nn.ReLU()))
+            setattr(self, "highway_gate%s" % i, nn.Sequential(Linear(D, D), nn.Sigmoid()))
+        self.context_LSTM = LSTM(input_size=D, hidden_size=H, bidirectional=True, batch_first=True, dropout=params["dropout"])
+        self.att_weight_c = Linear(H * 2, 1)
+        self.att_weight_q = Linear(H * 2, 1)
+        self.att_weight_cq = Linear(H * 2, 1)
+        self.modeling_LSTM1 = LSTM(input_size=H * 8, hidden_size=H, bidirectional=True, batch_first=True, dropout=params["dropout"])
+        self.dropout = nn.Dropout(p=params["dropout"])      # constructed, never applied (:45)
+        self.last_linear = _HeadLinear(2 * H, 1)
+        self.last_seeds = [None, None, None]
+
+    def _highway(self, x):
+        for i in range(2):
+            h_pre = getattr(self, "highway_linear%s" % i)[0](x)
+            g_pre = getattr(self, "highway_gate%s" % i)[0](x)
+            x = ops.highway(x, h_pre, g_pre)
+        return x
+
+    def forward(self, query: torch.Tensor, document: torch.Tensor, verbose=False, **kargs):
+        q_new, q_restoring, q_lens = kargs["query_lens_indices"]
+        d_new, d_restoring, c_lens = kargs["doc_lens_indices"]
+        q_word = self.word_emb(query.long())
+        c_word = self.word_emb(document.long())
+        _lib.require_cuda(q_word, c_word)
+        c = self._highway(c_word)
+        q = self._highway(q_word)
+        c = self.context_LSTM((c, c_lens, d_new, d_restoring))[0]
+        seed_c = self.context_LSTM.last_seed
+        q = self.context_LSTM((q, q_lens, q_new, q_restoring))[0]
+        seed_q = self.context_LSTM.last_seed
+        att = self.att_weight_c.linear, self.att_weight_q.linear, self.att_weight_cq.linear
+        g = ops.att_flow(c, q, att[0].weight, att[1].weight, att[2].weight, att[0].bias, att[1].bias, att[2].bias)
+        m = self.modeling_LSTM1((g, c_lens, d_new, d_restoring))[1]
+        self.last_seeds = [seed_c, seed_q, self.modeling_LSTM1.last_seed]
+        return self.last_linear(m)
+
+    def predict(self, query, doc, verbose: bool = False, **kargs):
+        assert KeyWordSettings.Query_lens in kargs and KeyWordSettings.Doc_lens in kargs
+        self.train(False)
+        dev = self.word_emb.weight.device
+
+        def lens_indices(lens):
+            lens = lens.detach().cpu().numpy() if torch.is_tensor(lens) else np.array(lens)
+            new = np.argsort(-lens)             # torch_utils.get_sorted_index_and_reverse_index: descending lengths and
+            return new, np.argsort(new), lens   # the permutation that restores the original order
+        out = self(torch.as_tensor(query).to(dev), torch.as_tensor(doc).to(dev), verbose=False,
+                   query_lens_indices=lens_indices(kargs[KeyWordSettings.Query_lens]),
+                   doc_lens_indices=lens_indices(kargs[KeyWordSettings.Doc_lens]))
+        return out.detach().cpu().numpy().flatten()

@@ -442,6 +442,53 @@ int gh_lstm_seq_bwd(const float* w_hh0, const float* w_hh1 /*NULL ok*/, const in
                     int n, int t_in, int t_out, int h, int dirs, const float* g_y /*NULL ok*/, int ldgy,
                     const float* g_hn /*NULL ok*/, const float* gates, const float* c, float* dgates, gh_stream_t stream);
 
+/* ---- the BiDAF model's own layers (get_amd/csrc/bidaf_ops.hip): Models/BiDAF/bidaf_model.py ----
+ * The attention-flow layer, replacing :72-104: the q_len calls of the 1-wide att_weight_cq over c * q_i and their stack
+ * (:75-83), the two expand adds (:87-89), both softmaxes (:92, :96), both bmm (:94, :98), the tiled expand (:100) and the
+ * four-way cat (:104).
+ *   c [b][lc][d] (row r of batch i at (i * lc + r) * ldc), q [b][lq][d] (ldq): read in place, e.g. column slices.
+ *   w_c, w_q, w_cq [d]: the weights of the three Linear(d, 1); b_c, b_q, b_cq: their 1-element biases as DEVICE pointers.
+ *   s[i][j] = c_i.w_c + q_j.w_q + (c_i * w_cq).q_j + (b_c + b_q + b_cq)
+ *   a = softmax_j(s) (running maximum subtracted), c2q_i = sum_j a_ij q_j
+ *   m_i = max_j s_ij, amax_i = the LOWEST j attaining it (torch.max's documented rule)
+ *   beta = softmax_i(m) over ALL lc rows of the batch element, q2c = sum_i beta_i c_i
+ *   x [b][lc][4d] (ldx >= 4d) = [c_i, c2q_i, c_i * c2q_i, c_i * q2c]
+ * THERE IS NO MASK, as in the reference: c and q are LSTM outputs with exact-zero rows at t >= len, and those rows take part
+ * in both softmaxes (a zero row of q scores c_i.w_c + bias, a zero row of c scores q_j.w_q + bias).
+ * Saved for the backward: a [b][lc][lq], amax [b][lc] int32, beta [b][lc], q2c [b][d]; m [b][lc] is scratch (the row maxima
+ * between the two launches).  c2q is re-read from x.
+ * Limits: lc <= 1024, lq <= 1024, d <= 2048, any b with b * ceil(max(lc, lq) / 16) < 2^31; anything beyond them is rejected
+ * with an error and nothing is written.  Rows that are 16-byte aligned (ld % 4 == 0, aligned base) move 16 bytes per lane,
+ * every other shape takes single-float accesses.  No atomics: two runs are bit-identical. */
+int gh_att_flow_fwd(const float* c, const float* q, int ldc, int ldq, const float* w_c, const float* w_q, const float* w_cq,
+                    const float* b_c, const float* b_q, const float* b_cq, int b, int lc, int lq, int d, float* x, int ldx,
+                    float* a, int32_t* amax, float* m /*scratch*/, float* beta, float* q2c, gh_stream_t stream);
+/* Backward of the above (autograd of :72-104) from g_x [b][lc][4d] (ldg), slices g0 .. g3:
+ *   dc2q = g1 + g2 * c;  dq2c = sum_i g3_i * c_i;  dbeta_i = dq2c.c_i;  dm_i = beta_i (dbeta_i - sum_k beta_k dbeta_k)
+ *   dA_ij = dc2q_i.q_j;  dS_ij = a_ij (dA_ij - sum_j a_ij dA_ij) + dm_i [j = amax_i]
+ *   dc_i = g0 + g2 * c2q + g3 * q2c + beta_i dq2c + dm_i w_c + w_cq * sum_j dS_ij q_j
+ *   dq_j = sum_i a_ij dc2q_i + (sum_i dS_ij) w_q + w_cq * sum_i dS_ij c_i
+ * ds [b][lc][lq], dm [b][lc] and dq2c [b][d] are scratch of the caller's.  Every element of dc (lddc) and dq (lddq) is
+ * written, nothing is accumulated there.  dw_c, dw_q, dw_cq [d] are ACCUMULATED (+=) from per-batch-element (dw_c) and
+ * per-(batch element, 16 query rows) partials, b * d * (1 + 2 ceil(lq / 16)) floats on the stream workspace, which must be
+ * registered (gh_set_stream_workspace / gh_set_workspace), summed by a second stage in a fixed order.
+ * The gradients of the three biases are mathematically zero (sum_j dS_ij = dm_i and sum_i dm_i = 0) and are not computed.
+ * Same limits as the forward. */
+int gh_att_flow_bwd(const float* c, const float* q, int ldc, int ldq, const float* w_c, const float* w_q, const float* w_cq,
+                    const float* x, int ldx, const float* a, const int32_t* amax, const float* beta, const float* q2c,
+                    const float* g_x, int ldg, int b, int lc, int lq, int d, float* ds /*scratch*/, float* dm /*scratch*/,
+                    float* dq2c /*scratch*/, float* dc, int lddc, float* dq, int lddq, float* dw_c /*ACCUMULATED*/,
+                    float* dw_q /*ACCUMULATED*/, float* dw_cq /*ACCUMULATED*/, gh_stream_t stream);
+/* The gate of the highway network (:62, with the ReLU and Sigmoid of the nn.Sequential holders :22-24 folded in), elementwise
+ * over [rows][d] contiguous tensors:  y = sigmoid(g_pre) relu(h_pre) + (1 - sigmoid(g_pre)) x.  h_pre and g_pre are the two
+ * projections of the layer (GEMMs of the caller's).  The sigmoid takes exp of non-positive arguments only: saturated
+ * pre-activations give exact 0 / 1 gates, never NaN. */
+int gh_highway_fwd(const float* x, const float* h_pre, const float* g_pre, int rows, int d, float* y, gh_stream_t stream);
+/* Backward from g [rows][d] in one launch: dh_pre = g s [h_pre > 0], dg_pre = g (relu(h_pre) - x) s (1 - s) and the direct
+ * dx = g (1 - s), s = sigmoid(g_pre); every element of the three is written. */
+int gh_highway_bwd(const float* x, const float* h_pre, const float* g_pre, const float* g, int rows, int d, float* dh_pre,
+                   float* dg_pre, float* dx, gh_stream_t stream);
+
 /* ---- a8  ragged helpers: Models/FCWithEvidences/basic_fc_model.py:80-121 ----
  * offsets[b+1] int32 prefix sum of evidence counts (device). */
 /* has[b] (NULL ok) = 1.0 for claims with at least one evidence: row 0 of pad_right(x) is x's first row of the claim times has. */
