@@ -59,6 +59,8 @@ SIGNATURES = {
     "gh_add_layernorm_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
     "gh_lstm_seq_fwd": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P],
     "gh_lstm_seq_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P],
+    "gh_gru_seq_fwd": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P],
+    "gh_gru_seq_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P],
     "gh_att_flow_fwd": [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P],
     "gh_att_flow_bwd": [_P, _P, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P,
                         _P, _P],

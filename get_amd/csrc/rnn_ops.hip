@@ -1,6 +1,9 @@
 // The recurrence of the LSTM sequence encoder (Models/BiDAF/wrapper.py:256-276, torch.nn.LSTM's cell equations):
 //   gh_lstm_seq_fwd   h_t, c_t over t from gx = x W_ih^T + b_ih + b_hh (a GEMM of the caller's) and W_hh
 //   gh_lstm_seq_bwd   dgates over t, walking time the other way
+// and of the GRU sequence encoder (wrapper.py:306-327, torch.nn.GRU's cell equations) in the same layout, further down:
+//   gh_gru_seq_fwd    h_t over t from gx = x W_ih^T + b_ih, W_hh and b_hh (b_hn sits inside the product with r: it cannot be folded)
+//   gh_gru_seq_bwd    the gradients of gx and of the recurrent pre-activations over t, walking time the other way
 // Only the sequential part lives here: the input projection, its gradients and dW_hh = dgates^T h_prev are activation-sized GEMMs
 // of gemm_ops.hip.  Both directions of a layer run in one launch (grid y).
 //
@@ -373,6 +376,251 @@ int lstm_check(const char* who, int n, int t_in, int t_out, int h, int dirs) {
   return 0;
 }
 
+// ============================================================================ GRU
+// torch.nn.GRU's cell, gate order r, z, n:  a = h_{t-1} W_hh^T + b_hh;  r = sigmoid(gx_r + a_r);  z = sigmoid(gx_z + a_z);
+// n = tanh(gx_n + r a_n);  h_t = (1 - z) n + z h_{t-1}.  The layout is the LSTM's with three gates and no cell state: what differs
+// is that b_hh is the kernel's (b_hn is multiplied by r), that the owning lane reads h_{t-1} once more for the convex update, and
+// that the backward has two gradient rows per step (of gx and of a: they differ in the n third by the factor r).
+constexpr int RNN_DA_PITCH = 3 * RNN_CHUNK + 4;              // [16][3][256] + 4: rows start 4 banks apart
+
+// ---------------------------------------------------------------------------- forward
+// grid (ceil(n / 16), dirs).  LDS: hs [2][16][pitch] | s_len [16] | s_row [16]
+__global__ __launch_bounds__(RNN_THREADS) void
+gru_fwd_kernel(const float* __restrict__ gx0, const float* __restrict__ gx1, long long ldgx, const float* __restrict__ w0,
+               const float* __restrict__ w1, const float* __restrict__ bh0, const float* __restrict__ bh1, const int32_t* __restrict__ lens,
+               const int32_t* __restrict__ order, int n, int t_in, int t_out, int h, float* __restrict__ y, long long ldy,
+               float* __restrict__ gates, float* __restrict__ ans, float* __restrict__ hprev, float* __restrict__ hn) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int pitch = rnn_pitch(h);
+  float* hs = sm;
+  int* s_len = reinterpret_cast<int*>(sm + 2 * RNN_TILE * pitch);
+  int* s_row = s_len + RNN_TILE;
+  const int dir = blockIdx.y;
+  const float* __restrict__ gx = dir ? gx1 : gx0;
+  const float* __restrict__ w = dir ? w1 : w0;
+  const float* __restrict__ bh = dir ? bh1 : bh0;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, qd = lane >> 4;
+  const bool vec = (h & 3) == 0;
+  const int h3 = 3 * h;
+  const int kp = up16(h), nut = kp >> 4;
+
+  const int tmax = tile_setup(s_len, s_row, lens, order, n, min(t_in, t_out));
+  for (int idx = threadIdx.x; idx < 2 * RNN_TILE * pitch; idx += RNN_THREADS) hs[idx] = 0.f;
+  // what no step writes: y beyond the length, h_prev of the first step and beyond the length, the state of an empty sequence
+  for (int i = 0; i < RNN_TILE; ++i) {
+    const int b = s_row[i], len = s_len[i];
+    if (b < 0) continue;
+    zero_rows(y + (size_t)b * t_out * ldy + (size_t)dir * h, ldy, len, t_out, h);
+    const size_t sr = ((size_t)dir * n + b) * t_in;
+    if (hprev) {
+      zero_rows(hprev + sr * h, h, len, t_in, h);
+      if (len > 0) zero_rows(hprev + sr * h, h, dir ? len - 1 : 0, dir ? len : 1, h);
+    }
+    for (int u = threadIdx.x; u < h; u += RNN_THREADS) hn[((size_t)dir * n + b) * h + u] = 0.f;
+  }
+  __syncthreads();
+
+  for (int s = 0; s < tmax; ++s) {
+    const int t = dir ? tmax - 1 - s : s;
+    const float* cur = hs + (s & 1) * RNN_TILE * pitch;
+    float* nxt = hs + ((s & 1) ^ 1) * RNN_TILE * pitch;
+    for (int ut = wave; ut < nut; ut += RNN_WAVES) {
+      const int u = ut * 16 + l15;
+      const bool uok = u < h;
+      // the input projection's share of the three pre-activations and the unit's recurrent biases, fetched ahead of the k loop
+      float px[3][4], bu[3];
+      bool act[4];
+#pragma unroll
+      for (int g = 0; g < 3; ++g) bu[g] = uok ? bh[g * h + u] : 0.f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = 4 * qd + r, b = s_row[i];
+        act[r] = b >= 0 && t < s_len[i] && uok;
+        const float* p = gx + ((size_t)(act[r] ? b : 0) * t_in + (act[r] ? t : 0)) * ldgx + (uok ? u : 0);
+#pragma unroll
+        for (int g = 0; g < 3; ++g) px[g][r] = act[r] ? p[g * h] : 0.f;
+      }
+      f32x4 acc[3];
+#pragma unroll
+      for (int g = 0; g < 3; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+      const float* wrow = w + (size_t)(uok ? u : 0) * h;
+      const float* ap = cur + l15 * pitch + 4 * qd;
+      // operands of the next 16-deep k step are requested before this step's MFMAs are issued
+      float4 a4 = *reinterpret_cast<const float4*>(ap);
+      float4 b4[3];
+#pragma unroll
+      for (int g = 0; g < 3; ++g) b4[g] = uok ? load_w4(wrow + (size_t)g * h * h, 4 * qd, h, vec) : make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int k0 = 0; k0 < kp; k0 += 16) {
+        const int kn = k0 + 16;
+        float4 an = a4, bn[3];
+        if (kn < kp) an = *reinterpret_cast<const float4*>(ap + kn);
+#pragma unroll
+        for (int g = 0; g < 3; ++g) bn[g] = uok ? load_w4(wrow + (size_t)g * h * h, kn + 4 * qd, h, vec) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int g = 0; g < 3; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.x, b4[g].x, acc[g], 0, 0, 0);
+#pragma unroll
+        for (int g = 0; g < 3; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.y, b4[g].y, acc[g], 0, 0, 0);
+#pragma unroll
+        for (int g = 0; g < 3; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.z, b4[g].z, acc[g], 0, 0, 0);
+#pragma unroll
+        for (int g = 0; g < 3; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.w, b4[g].w, acc[g], 0, 0, 0);
+        a4 = an;
+#pragma unroll
+        for (int g = 0; g < 3; ++g) b4[g] = bn[g];
+      }
+      // C/D map: column (unit) = lane & 15, row (sequence) = 4 (lane >> 4) + r
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = 4 * qd + r;
+        float hv = 0.f;
+        if (act[r]) {
+          const int b = s_row[i], len = s_len[i];
+          const float hp = cur[i * pitch + u];              // h_{t-1}, from the buffer the A operand was read from
+          const float av = acc[2][r] + bu[2];
+          const float rg = rnn_sigmoid(px[0][r] + (acc[0][r] + bu[0]));
+          const float zg = rnn_sigmoid(px[1][r] + (acc[1][r] + bu[1]));
+          const float ng = tanhf(px[2][r] + rg * av);
+          hv = (1.f - zg) * ng + zg * hp;
+          y[((size_t)b * t_out + t) * ldy + (size_t)dir * h + u] = hv;
+          const size_t sq = (size_t)dir * n + b;
+          if (gates) {
+            const size_t sr = sq * t_in + t;
+            float* gp = gates + sr * h3 + u;
+            gp[0] = rg;
+            gp[h] = zg;
+            gp[2 * h] = ng;
+            ans[sr * h + u] = av;
+            if (dir ? t >= 1 : t + 1 < len) hprev[(dir ? sr - 1 : sr + 1) * h + u] = hv;
+          }
+          hn[sq * h + u] = hv;
+        }
+        if (uok) nxt[i * pitch + u] = hv;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------- backward
+// grid (ceil(n / 16), dirs).  LDS: das [16][RNN_DA_PITCH] | s_len [16] | s_row [16]
+__global__ __launch_bounds__(RNN_THREADS) void
+gru_bwd_kernel(const float* __restrict__ w0, const float* __restrict__ w1, const int32_t* __restrict__ lens,
+               const int32_t* __restrict__ order, int n, int t_in, int t_out, int h, const float* __restrict__ gy, long long ldgy,
+               const float* __restrict__ ghn, const float* __restrict__ gates, const float* __restrict__ ans,
+               const float* __restrict__ hprev, float* __restrict__ dgx, float* __restrict__ da) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float* das = sm;
+  int* s_len = reinterpret_cast<int*>(sm + RNN_TILE * RNN_DA_PITCH);
+  int* s_row = s_len + RNN_TILE;
+  const int dir = blockIdx.y;
+  const float* __restrict__ w = dir ? w1 : w0;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, qd = lane >> 4;
+  const bool vec = (h & 1) == 0;
+  const int h3 = 3 * h;
+
+  const int tmax = tile_setup(s_len, s_row, lens, order, n, min(t_in, t_out));
+  for (int idx = threadIdx.x; idx < RNN_TILE * RNN_DA_PITCH; idx += RNN_THREADS) das[idx] = 0.f;
+  for (int i = 0; i < RNN_TILE; ++i) {
+    const int b = s_row[i];
+    if (b < 0) continue;
+    zero_rows(dgx + ((size_t)dir * n + b) * t_in * h3, h3, s_len[i], t_in, h3);
+    zero_rows(da + ((size_t)dir * n + b) * t_in * h3, h3, s_len[i], t_in, h3);
+  }
+  __syncthreads();
+
+  // lane (l15, qd) of wave w owns, for p < RNN_BWD_NP: sequences 4 qd + r, units 32 (8 p + w) + 2 l15 + cc
+  f32x4 dh[RNN_BWD_NP][2];
+#pragma unroll
+  for (int p = 0; p < RNN_BWD_NP; ++p) dh[p][0] = dh[p][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  for (int s = 0; s < tmax; ++s) {
+    const int t = dir ? s : tmax - 1 - s;
+    // the next step's dh: the direct part dh z is added by the owning lane when it forms its chunk's gradients, the product
+    // [dr_pre, dz_pre, da_n] W_hh by the MFMAs of every chunk
+    f32x4 acc[RNN_BWD_NP][2];
+#pragma unroll
+    for (int p = 0; p < RNN_BWD_NP; ++p) acc[p][0] = acc[p][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int p = 0; p < RNN_BWD_NP; ++p) {
+      const int u0 = p * RNN_CHUNK;                 // first unit of the chunk
+      if (u0 >= h) continue;
+      // ---- both gradient rows of the chunk's units from dh = g_y + dh_carry (+ g_hn at the sequence's last forward step)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = 4 * qd + r, b = s_row[i], len = s_len[i];
+        const bool live = b >= 0 && t < len;
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc) {
+          const int uu = wave * RNN_GW + 2 * l15 + cc, u = u0 + uu;
+          float dr = 0.f, dz = 0.f, dan = 0.f;
+          if (live && u < h) {
+            const size_t sq = (size_t)dir * n + b, sr = sq * t_in + t;
+            const float* gp = gates + sr * h3 + u;
+            const float rg = gp[0], zg = gp[h], ng = gp[2 * h];
+            const float av = ans[sr * h + u], hp = hprev[sr * h + u];
+            float dhv = dh[p][cc][r];
+            if (gy) dhv += gy[((size_t)b * t_out + t) * ldgy + (size_t)dir * h + u];
+            if (ghn && (dir ? t == 0 : t == len - 1)) dhv += ghn[sq * h + u];
+            const float dnp = dhv * (1.f - zg) * (1.f - ng * ng);
+            dz = dhv * (hp - ng) * zg * (1.f - zg);
+            dr = dnp * av * rg * (1.f - rg);
+            dan = dnp * rg;
+            acc[p][cc][r] += dhv * zg;
+            float* xp = dgx + sr * h3 + u;
+            xp[0] = dr;
+            xp[h] = dz;
+            xp[2 * h] = dnp;
+            float* rp = da + sr * h3 + u;
+            rp[0] = dr;
+            rp[h] = dz;
+            rp[2 * h] = dan;
+          }
+          float* ds = das + i * RNN_DA_PITCH + uu;
+          ds[0] = dr;
+          ds[RNN_CHUNK] = dz;
+          ds[2 * RNN_CHUNK] = dan;
+        }
+      }
+      __syncthreads();
+      // ---- dh_carry[.][units of this wave's groups] += da_chunk W_hh[rows of the chunk]
+      const int ucp = min(RNN_CHUNK, h - u0);
+      for (int g = 0; g < 3; ++g) {
+        const float* ap = das + l15 * RNN_DA_PITCH + g * RNN_CHUNK + qd;
+        const float* wg = w + ((size_t)g * h + u0 + qd) * h;
+        // blocks of RNN_BWD_PF k steps; the next block's operands are requested before this block's MFMAs are issued
+        float a[RNN_BWD_PF];
+        float2 b2[RNN_BWD_PF][RNN_BWD_NP];
+        bwd_operands(a, b2, ap, wg, 0, ucp, qd, wave, l15, h, vec);
+        for (int k0 = 0; k0 < ucp; k0 += 4 * RNN_BWD_PF) {
+          float an[RNN_BWD_PF];
+          float2 bn[RNN_BWD_PF][RNN_BWD_NP];
+          bwd_operands(an, bn, ap, wg, k0 + 4 * RNN_BWD_PF, ucp, qd, wave, l15, h, vec);
+#pragma unroll
+          for (int e = 0; e < RNN_BWD_PF; ++e)
+#pragma unroll
+            for (int q = 0; q < RNN_BWD_NP; ++q)
+              if ((q * RNN_WAVES + wave) * RNN_GW < h) {
+                acc[q][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b2[e][q].x, acc[q][0], 0, 0, 0);
+                acc[q][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b2[e][q].y, acc[q][1], 0, 0, 0);
+              }
+#pragma unroll
+          for (int e = 0; e < RNN_BWD_PF; ++e) {
+            a[e] = an[e];
+#pragma unroll
+            for (int q = 0; q < RNN_BWD_NP; ++q) b2[e][q] = bn[e][q];
+          }
+        }
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int p = 0; p < RNN_BWD_NP; ++p) {
+      dh[p][0] = acc[p][0];
+      dh[p][1] = acc[p][1];
+    }
+  }
+}
+
 }  // namespace
 }  // namespace gh
 
@@ -408,6 +656,41 @@ extern "C" int gh_lstm_seq_bwd(const float* w_hh0, const float* w_hh1, const int
   if (int rc = lds_opt_in(lstm_bwd_kernel, lds, "lstm_seq_bwd")) return rc;
   hipLaunchKernelGGL(lstm_bwd_kernel, dim3((n + RNN_TILE - 1) / RNN_TILE, dirs), dim3(RNN_THREADS), lds, st, w_hh0, w_hh1, lens, order, n,
                      t_in, t_out, h, g_y, (long long)ldgy, g_hn, gates, c, dgates);
+  GH_LAUNCH_CHECK();
+  return 0;
+}
+
+// (lstm_check names nothing of the LSTM's: the limits and their messages are those of both recurrences)
+extern "C" int gh_gru_seq_fwd(const float* gx0, const float* gx1, int ldgx, const float* w_hh0, const float* w_hh1, const float* b_hh0,
+                              const float* b_hh1, const int32_t* lens, const int32_t* order, int n, int t_in, int t_out, int h, int dirs,
+                              float* y, int ldy, float* gates, float* an, float* h_prev, float* h_n, gh_stream_t stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = lstm_check("gru_seq_fwd", n, t_in, t_out, h, dirs)) return rc;
+  GH_REQUIRE(gx0 && w_hh0 && b_hh0 && lens && y && h_n && (dirs == 1 || (gx1 && w_hh1 && b_hh1)), "gru_seq_fwd: NULL argument");
+  GH_REQUIRE((gates != nullptr) == (an != nullptr) && (gates != nullptr) == (h_prev != nullptr),
+             "gru_seq_fwd: gates, an and h_prev are saved together or not at all");
+  GH_REQUIRE(ldgx >= 3 * h && ldy >= dirs * h, "gru_seq_fwd: a leading dimension is smaller than its row");
+  GH_REQUIRE(aligned16(w_hh0) && aligned16(w_hh1), "gru_seq_fwd: w_hh must be 16-byte aligned");
+  const size_t lds = ((size_t)2 * RNN_TILE * rnn_pitch(h) + 2 * RNN_TILE) * sizeof(float);
+  if (int rc = lds_opt_in(gru_fwd_kernel, lds, "gru_seq_fwd")) return rc;
+  hipLaunchKernelGGL(gru_fwd_kernel, dim3((n + RNN_TILE - 1) / RNN_TILE, dirs), dim3(RNN_THREADS), lds, st, gx0, gx1, (long long)ldgx,
+                     w_hh0, w_hh1, b_hh0, b_hh1, lens, order, n, t_in, t_out, h, y, (long long)ldy, gates, an, h_prev, h_n);
+  GH_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gh_gru_seq_bwd(const float* w_hh0, const float* w_hh1, const int32_t* lens, const int32_t* order, int n, int t_in,
+                              int t_out, int h, int dirs, const float* g_y, int ldgy, const float* g_hn, const float* gates,
+                              const float* an, const float* h_prev, float* dgx, float* da, gh_stream_t stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = lstm_check("gru_seq_bwd", n, t_in, t_out, h, dirs)) return rc;
+  GH_REQUIRE(w_hh0 && lens && gates && an && h_prev && dgx && da && (dirs == 1 || w_hh1), "gru_seq_bwd: NULL argument");
+  GH_REQUIRE(!g_y || ldgy >= dirs * h, "gru_seq_bwd: ldgy is smaller than dirs * h");
+  GH_REQUIRE(aligned16(w_hh0) && aligned16(w_hh1), "gru_seq_bwd: w_hh must be 16-byte aligned");
+  const size_t lds = ((size_t)RNN_TILE * RNN_DA_PITCH + 2 * RNN_TILE) * sizeof(float);
+  if (int rc = lds_opt_in(gru_bwd_kernel, lds, "gru_seq_bwd")) return rc;
+  hipLaunchKernelGGL(gru_bwd_kernel, dim3((n + RNN_TILE - 1) / RNN_TILE, dirs), dim3(RNN_THREADS), lds, st, w_hh0, w_hh1, lens, order, n,
+                     t_in, t_out, h, g_y, (long long)ldgy, g_hn, gates, an, h_prev, dgx, da);
   GH_LAUNCH_CHECK();
   return 0;
 }

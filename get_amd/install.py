@@ -21,7 +21,7 @@ def install():
 
     # Models.BiDAF.wrapper  (master_get -> graph_based_semantic_structure.py:8)
     _module("Models.BiDAF.wrapper", GGNN=M.GGNN, GGNN_with_GSL=M.GGNN_with_GSL, GSL=M.GSL, Linear=M.Linear,
-            LSTM=M.LSTM, GraphAttentionLayer=M.GraphAttentionLayer, GAT=M.GAT, GCN=M.GCN, torch=torch, nn=nn)
+            LSTM=M.LSTM, GRU=M.GRU, GraphAttentionLayer=M.GraphAttentionLayer, GAT=M.GAT, GCN=M.GCN, torch=torch, nn=nn)
     # thirdparty.two_branches_attention is star-imported by the model module (:9), which is also
     # where that module gets `nn` and `np` from
     _module("thirdparty.two_branches_attention", ConcatNotEqualSelfAtt=M.ConcatNotEqualSelfAtt,

@@ -4,7 +4,7 @@ Same class names, constructor arguments, ``forward()`` signatures, parameter nam
 as upstream, so ``MasterFC/master_get.py`` and reference checkpoints
 load unchanged:
 
-  Models/BiDAF/wrapper.py                      Linear, GGNN, GSL, GGNN_with_GSL, LSTM,
+  Models/BiDAF/wrapper.py                      Linear, GGNN, GSL, GGNN_with_GSL, LSTM, GRU,
                                                GraphAttentionLayer, GAT, GCN
   thirdparty/two_branches_attention.py         ConcatNotEqualSelfAtt, ConcatSelfAtt, Dot, BiLinear, BiLinearTanh,
                                                ScaledDotProductAttention, MultiHeadAttentionOriginal,
@@ -267,22 +267,7 @@ class LSTM(nn.Module):
                 nn.init.constant_(getattr(self.rnn, "bias_ih_l%s%s" % (i, sfx)), val=0)
 
     def forward(self, x, return_h=True, max_len=None):
-        x, x_len, d_new_indices, d_restoring_indices = x
-        assert x.dim() == 3, "LSTM: x is (B, L, D)"
-        x_len = torch.as_tensor(x_len)
-        assert x_len.shape == (x.shape[0],) and not x_len.dtype.is_floating_point, "LSTM: x_len is an integer (B,) tensor"
-        if max_len is not None:
-            T = int(max_len)
-        else:
-            T = int(x_len.max())        # (a device x_len is read back here; the model always passes max_len)
-        if not x_len.is_cuda and (int(x_len.max()) > T or int(x_len.min()) < 1):
-            raise ValueError("LSTM: every length must lie in [1, %d], got [%d, %d]" % (T, int(x_len.min()), int(x_len.max())))
-        _lib.require_cuda(x)
-        lens = x_len.to(device=x.device, dtype=torch.int32, non_blocking=True)
-        order = torch.as_tensor(d_new_indices).to(device=x.device, dtype=torch.int32, non_blocking=True)
-        p, seed = _encoder_drop(self.training, self.dropout.p)
-        self.last_seed = seed if p > 0 else None
-        inp = ops.feat_dropout(x, p, seed)
+        inp, lens, order, T, d_new_indices = _rnn_inputs(self, "LSTM", x, max_len)
         states = []
         for i in range(self.rnn.num_layers):
             gx, w_hh = [], []
@@ -292,12 +277,91 @@ class LSTM(nn.Module):
                 w_hh.append(getattr(self.rnn, "weight_hh_l%s%s" % (i, sfx)))
             inp, h_n, _ = ops.lstm_seq(gx, w_hh, lens, order, T)
             states.append(h_n)
-        h = states[0] if len(states) == 1 else torch.cat(states, dim=0)
-        if return_h:
-            h = h.permute(1, 0, 2).reshape(h.shape[1], -1)
-        else:
-            h = h[:, torch.as_tensor(d_new_indices).to(x.device).long()]
-        return inp, h
+        return inp, _rnn_state(states, return_h, d_new_indices)
+
+
+def _rnn_inputs(module, who, x, max_len):
+    """The argument handling LSTM.forward and GRU.forward share: the 4-tuple, T, the host-side length check, the device
+    lengths and tiling order, the input dropout with its seed kept in ``module.last_seed``."""
+    x, x_len, d_new_indices, d_restoring_indices = x
+    assert x.dim() == 3, who + ": x is (B, L, D)"
+    x_len = torch.as_tensor(x_len)
+    assert x_len.shape == (x.shape[0],) and not x_len.dtype.is_floating_point, who + ": x_len is an integer (B,) tensor"
+    if max_len is not None:
+        T = int(max_len)
+    else:
+        T = int(x_len.max())        # (a device x_len is read back here; the model always passes max_len)
+    if not x_len.is_cuda and (int(x_len.max()) > T or int(x_len.min()) < 1):
+        raise ValueError("%s: every length must lie in [1, %d], got [%d, %d]" % (who, T, int(x_len.min()), int(x_len.max())))
+    _lib.require_cuda(x)
+    lens = x_len.to(device=x.device, dtype=torch.int32, non_blocking=True)
+    order = torch.as_tensor(d_new_indices).to(device=x.device, dtype=torch.int32, non_blocking=True)
+    p, seed = _encoder_drop(module.training, module.dropout.p)
+    module.last_seed = seed if p > 0 else None
+    return ops.feat_dropout(x, p, seed), lens, order, T, d_new_indices
+
+
+def _rnn_state(states, return_h, d_new_indices):
+    """The second value of the two encoders from the per-layer (dirs, B, H) final states: (B, layers*dirs*H) in the rows of x
+    when return_h, else the raw (layers*dirs, B, H) tensor in the sorted order."""
+    h = states[0] if len(states) == 1 else torch.cat(states, dim=0)
+    if return_h:
+        return h.permute(1, 0, 2).reshape(h.shape[1], -1)
+    return h[:, torch.as_tensor(d_new_indices).to(h.device).long()]
+
+
+# ------------------------------------------------------------------ Models/BiDAF/wrapper.py:279-327
+class GRU(nn.Module):
+    """The reference's GRU sequence encoder on the HIP recurrence kernels (ops.gru_seq).  ``self.rnn`` only holds the
+    parameters (state_dict keys ``rnn.weight_ih_l0`` ...): it is never called, neither MIOpen nor nn.GRU.forward runs.
+
+    This is the reference's constructor with its one raising line made runnable: upstream's ``reset_params`` ends each layer and
+    direction with ``bias_hh.chunk(4)[1].fill_(1)`` on a leaf parameter that requires grad, which raises, so upstream's class
+    cannot be constructed as written.  Here the same statements run in the same order under ``torch.no_grad()`` -- the
+    one-line repair a user of the reference makes.  ``chunk(4)`` of the 3H-vector gives pieces of ceil(3H/4) elements, so the
+    ones land on elements [ceil(3H/4), 2 ceil(3H/4)): they straddle the r and z thirds (the tail of r, the head of z), not
+    one gate as the LSTM-style forget-bias idiom intends.  That is kept exactly as written.
+
+    forward((x, x_len, d_new_indices, d_restoring_indices), return_h=True, max_len=None): the contract of :class:`LSTM` --
+    T, the host-side ValueError for lengths outside [1, T], device lengths clamped (a length of 0 gives zero rows and a zero
+    state), d_new_indices used only as tiling order, outputs in the rows of x, y (B,T,dirs*H) zero at t >= len, h as there.
+    Training mode: input dropout by ops.feat_dropout with its seed kept in ``last_seed``; no dropout between layers."""
+
+    def __init__(self, input_size, hidden_size, batch_first=False, num_layers=1, bidirectional=False, dropout=0.2):
+        super().__init__()
+        _drop_caches_on_load(self)
+        self.rnn = nn.GRU(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers,
+                          bidirectional=bidirectional, batch_first=batch_first)
+        self.reset_params()
+        self.dropout = nn.Dropout(p=dropout)
+        self.last_seed = None       # input-dropout seed of the last training-mode forward (ops.feat_dropout)
+
+    def _suffixes(self):
+        return ("", "_reverse") if self.rnn.bidirectional else ("",)
+
+    def reset_params(self):
+        # wrapper.py:291-304, statement by statement, under no_grad (the fill_ of a view of a leaf raises otherwise)
+        with torch.no_grad():
+            for i in range(self.rnn.num_layers):
+                for sfx in self._suffixes():
+                    nn.init.orthogonal_(getattr(self.rnn, "weight_hh_l%s%s" % (i, sfx)))
+                    nn.init.kaiming_normal_(getattr(self.rnn, "weight_ih_l%s%s" % (i, sfx)))
+                    nn.init.constant_(getattr(self.rnn, "bias_hh_l%s%s" % (i, sfx)), val=0)
+                    nn.init.constant_(getattr(self.rnn, "bias_ih_l%s%s" % (i, sfx)), val=0)
+                    getattr(self.rnn, "bias_hh_l%s%s" % (i, sfx)).chunk(4)[1].fill_(1)
+
+    def forward(self, x, return_h=True, max_len=None):
+        inp, lens, order, T, d_new_indices = _rnn_inputs(self, "GRU", x, max_len)
+        states = []
+        for i in range(self.rnn.num_layers):
+            gx, w_hh, b_hh = [], [], []
+            for sfx in self._suffixes():
+                gx.append(ops.linear(inp, getattr(self.rnn, "weight_ih_l%s%s" % (i, sfx)), getattr(self.rnn, "bias_ih_l%s%s" % (i, sfx))))
+                w_hh.append(getattr(self.rnn, "weight_hh_l%s%s" % (i, sfx)))
+                b_hh.append(getattr(self.rnn, "bias_hh_l%s%s" % (i, sfx)))
+            inp, h_n = ops.gru_seq(gx, w_hh, b_hh, lens, order, T)
+            states.append(h_n)
+        return inp, _rnn_state(states, return_h, d_new_indices)
 
 
 # ------------------------------------------------------------------ Models/BiDAF/wrapper.py:7-67

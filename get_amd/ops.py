@@ -1015,6 +1015,87 @@ def lstm_seq(gx, w_hh, lens, order, t_out: int):
     return _LstmSeq.apply(gx[0], gx[1] if len(gx) == 2 else None, w_hh[0], w_hh[1] if len(gx) == 2 else None, lens, order, int(t_out))
 
 
+# --------------------------------------------------------------------------- GRU recurrence (wrapper.py:306-327)
+class _GruSeq(torch.autograd.Function):
+    """One layer's recurrence, both directions in one launch: csrc/rnn_ops.hip gh_gru_seq_*.  The backward kernel writes the
+    gradient of gx and the gradient `da` of the recurrent pre-activations (they differ in the n third by the factor r);
+    dW_hh = da^T h_prev and db_hh = colsum(da) are ONE call of the weight-gradient GEMM per direction (gh_linear_bwd without dx)."""
+
+    @staticmethod
+    def forward(ctx, gx0, gx1, w0, w1, b0, b1, lens, order, t_out):
+        _lib.require_cuda(gx0, gx1, w0, w1, b0, b1, lens, order)
+        dirs = 1 if gx1 is None else 2
+        shapes = "gru_seq: gx (N,T,3H), w_hh (3H,H), b_hh (3H,) per direction"
+        assert gx0.dim() == 3 and w0.dim() == 2 and b0 is not None and (w1 is None) == (gx1 is None) and (b1 is None) == (gx1 is None), shapes
+        n, t_in, h3 = gx0.shape
+        h = w0.shape[1]
+        assert h3 == 3 * h and w0.shape[0] == h3 and b0.shape == (h3,) and \
+            (dirs == 1 or (gx1.shape == gx0.shape and w1.shape == w0.shape and b1.shape == b0.shape)), shapes
+        assert lens.dtype == torch.int32 and lens.shape == (n,) and (order is None or (order.dtype == torch.int32 and order.shape == (n,))), \
+            "gru_seq: lens and order are int32 (N,)"
+        gx0 = _f32(gx0)
+        gx1 = _f32(gx1) if gx1 is not None else None
+        wc0, bc0 = _f32(w0.detach()), _f32(b0.detach())
+        wc1 = _f32(w1.detach()) if w1 is not None else None
+        bc1 = _f32(b1.detach()) if b1 is not None else None
+        lens, order = lens.contiguous(), (order.contiguous() if order is not None else None)
+        dev = gx0.device
+        y = torch.empty((n, t_out, dirs * h), device=dev, dtype=torch.float32)
+        hn = torch.empty((dirs, n, h), device=dev, dtype=torch.float32)
+        gates = an = hprev = None
+        if any(ctx.needs_input_grad[:6]):
+            gates = torch.empty((dirs, n, t_in, h3), device=dev, dtype=torch.float32)
+            an = torch.empty((dirs, n, t_in, h), device=dev, dtype=torch.float32)
+            hprev = torch.empty((dirs, n, t_in, h), device=dev, dtype=torch.float32)
+        call("gh_gru_seq_fwd", ptr(gx0), ptr(gx1), h3, ptr(wc0), ptr(wc1), ptr(bc0), ptr(bc1), ptr(lens), ptr(order), n, t_in, t_out, h,
+             dirs, ptr(y), dirs * h, ptr(gates), ptr(an), ptr(hprev), ptr(hn), stream())
+        ctx.dims = (n, t_in, t_out, h, dirs)
+        ctx.params = (w0, w1, b0, b1)
+        ctx.save_for_backward(wc0, wc1, lens, order, gates, an, hprev)
+        ctx.set_materialize_grads(False)
+        return y, hn
+
+    @staticmethod
+    def backward(ctx, g_y, g_hn):
+        wc0, wc1, lens, order, gates, an, hprev = ctx.saved_tensors
+        n, t_in, t_out, h, dirs = ctx.dims
+        g_y = _f32(g_y) if g_y is not None else None
+        g_hn = _f32(g_hn) if g_hn is not None else None
+        dgx, da = torch.empty_like(gates), torch.empty_like(gates)
+        call("gh_gru_seq_bwd", ptr(wc0), ptr(wc1), ptr(lens), ptr(order), n, t_in, t_out, h, dirs, ptr(g_y), dirs * h, ptr(g_hn),
+             ptr(gates), ptr(an), ptr(hprev), ptr(dgx), ptr(da), stream())
+        dws, dbs = [None, None], [None, None]
+        for d in range(dirs):
+            need_w, need_b = ctx.needs_input_grad[2 + d], ctx.needs_input_grad[4 + d]
+            if not (need_w or need_b):
+                continue
+            _lib.ensure_workspace(da.device)
+            pw, pb = ctx.params[d], ctx.params[2 + d]
+            direct = need_w and need_b and _direct(pw) and _direct(pb)
+            if direct:
+                dw, db = pw.grad, pb.grad
+            else:
+                dw = torch.zeros((3 * h, h), device=da.device, dtype=torch.float32)
+                db = torch.zeros((3 * h,), device=da.device, dtype=torch.float32)
+            call("gh_linear_bwd", ptr(hprev[d]), None, None, ptr(da[d]), n * t_in, h, 3 * h, None, ptr(dw), ptr(db), stream())
+            if not direct:
+                dws[d], dbs[d] = (dw if need_w else None), (db if need_b else None)
+        return dgx[0], (dgx[1] if dirs == 2 else None), dws[0], dws[1], dbs[0], dbs[1], None, None, None
+
+
+def gru_seq(gx, w_hh, b_hh, lens, order, t_out: int):
+    """The recurrence of one GRU layer.  gx / w_hh / b_hh: one tensor per direction (forward, then reverse) -- gx (N,T_in,3H) =
+    x W_ih^T + b_ih ALONE in torch's gate order r, z, n; w_hh (3H,H) and b_hh (3H,) as nn.GRU stores them (b_hh stays with the
+    kernel: its n third is multiplied by r); lens (N,) int32 on the device (clamped into [0, min(T_in, t_out)]); order (N,)
+    int32 or None: the processing order, outputs stay in the rows of the inputs.  Returns y (N,t_out,dirs*H) with exact zeros
+    at t >= len and h_n (dirs,N,H); differentiable in gx, w_hh and b_hh."""
+    gx, w_hh, b_hh = list(gx), list(w_hh), list(b_hh)
+    assert len(gx) == len(w_hh) == len(b_hh) and len(gx) in (1, 2), "gru_seq: one or two directions"
+    two = len(gx) == 2
+    return _GruSeq.apply(gx[0], gx[1] if two else None, w_hh[0], w_hh[1] if two else None, b_hh[0], b_hh[1] if two else None, lens, order,
+                         int(t_out))
+
+
 # --------------------------------------------------------------------------- BiDAF: attention flow and highway gate
 class _OutBuffer:
     """The caller's destination of ops.att_flow, handed to the autograd function as a plain object: the buffer is where the

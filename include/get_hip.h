@@ -442,6 +442,39 @@ int gh_lstm_seq_bwd(const float* w_hh0, const float* w_hh1 /*NULL ok*/, const in
                     int n, int t_in, int t_out, int h, int dirs, const float* g_y /*NULL ok*/, int ldgy,
                     const float* g_hn /*NULL ok*/, const float* gates, const float* c, float* dgates, gh_stream_t stream);
 
+/* ---- the GRU sequence encoder's recurrence (get_amd/csrc/rnn_ops.hip): Models/BiDAF/wrapper.py:306-327 ----
+ * What pack_padded_sequence + nn.GRU + pad_packed_sequence + the two index gathers of :310-326 compute for ONE layer, both
+ * directions in one launch, with torch.nn.GRU's cell equations (gate order r, z, n; zero initial state):
+ *   a = h_{t-1} W_hh^T + b_hh;  r = sigmoid(gx_r + a_r);  z = sigmoid(gx_z + a_z);  n = tanh(gx_n + r a_n);
+ *   h_t = (1 - z) n + z h_{t-1}
+ * gx0 / gx1 [n][t_in][3h] (row pitch ldgx >= 3h): the input projection x W_ih^T + b_ih ALONE of the forward / the reverse
+ * direction (gx1, w_hh1, b_hh1: NULL when dirs == 1), a GEMM of the caller's.  b_hh cannot be folded into gx as for the LSTM:
+ * its n third is multiplied by r.  w_hh [3h][h] as nn.GRU stores it, 16-byte aligned; b_hh0 / b_hh1 [3h] DEVICE pointers.
+ * lens, order, the clamping, the row addressing and the reverse direction's walk are those of gh_lstm_seq_fwd.
+ * Out: y [n][t_out][ldy] columns [dir * h, (dir + 1) * h), exact zeros at t >= len (also in rows [t_in, t_out)); h_n [dirs][n][h]
+ * (the state after the last step of the direction; zeros for an empty sequence).  Saved for the backward when all three are
+ * given (all NULL: inference): gates [dirs][n][t_in][3h] (post-activation r, z, n), an [dirs][n][t_in][h] (a_n, b_hn included)
+ * and h_prev [dirs][n][t_in][h] (the hidden state that ENTERED step t, zeros at t >= len).  Rows t >= len of gates and an are
+ * not written.  The sigmoid takes exp of non-positive arguments only: saturated pre-activations give exact 0 / 1, never NaN.
+ * Limits: h <= 1024, t_in <= 4096, t_out <= 4096, dirs 1 or 2, any n; anything beyond is rejected and nothing is written. */
+int gh_gru_seq_fwd(const float* gx0, const float* gx1 /*NULL ok*/, int ldgx, const float* w_hh0, const float* w_hh1 /*NULL ok*/,
+                   const float* b_hh0, const float* b_hh1 /*NULL ok*/, const int32_t* lens, const int32_t* order /*NULL ok*/,
+                   int n, int t_in, int t_out, int h, int dirs, float* y, int ldy, float* gates /*NULL ok*/,
+                   float* an /*NULL ok*/, float* h_prev /*NULL ok*/, float* h_n, gh_stream_t stream);
+/* Backward of the above (autograd of torch.nn.GRU's cell equations) from g_y [n][t_out][ldgy] (NULL ok) and g_hn [dirs][n][h]
+ * (NULL ok), walking time the other way.  With dh = g_y[t] + dh_carry (+ g_hn at the direction's last step):
+ *   dn_pre = dh (1 - z) (1 - n^2);  dz_pre = dh (h_prev - n) z (1 - z);  dr_pre = dn_pre a_n r (1 - r);  da_n = dn_pre r;
+ *   dh_carry = dh z + [dr_pre, dz_pre, da_n] W_hh
+ * Two outputs, each [dirs][n][t_in][3h], every element written, exact zeros at t >= len:
+ *   dgx = [dr_pre, dz_pre, dn_pre]   the gradient of gx (db_ih, dW_ih and dx follow from the input projection's backward)
+ *   da  = [dr_pre, dz_pre, da_n]     the gradient of the recurrent pre-activations a
+ * The caller forms dW_hh = da^T h_prev AND db_hh = colsum(da) per direction with ONE gh_linear_bwd (dx = NULL, x = h_prev,
+ * g = da, dw, db).  No atomics: every element has one owner, two runs are bit-identical.  Same limits as the forward. */
+int gh_gru_seq_bwd(const float* w_hh0, const float* w_hh1 /*NULL ok*/, const int32_t* lens, const int32_t* order /*NULL ok*/,
+                   int n, int t_in, int t_out, int h, int dirs, const float* g_y /*NULL ok*/, int ldgy,
+                   const float* g_hn /*NULL ok*/, const float* gates, const float* an, const float* h_prev, float* dgx,
+                   float* da, gh_stream_t stream);
+
 /* ---- the BiDAF model's own layers (get_amd/csrc/bidaf_ops.hip): Models/BiDAF/bidaf_model.py ----
  * The attention-flow layer, replacing :72-104: the q_len calls of the 1-wide att_weight_cq over c * q_i and their stack
  * (:75-83), the two expand adds (:87-89), both softmaxes (:92, :96), both bmm (:94, :98), the tiled expand (:100) and the
