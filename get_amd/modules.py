@@ -225,8 +225,53 @@ class GGNN_with_GSL(nn.Module):
         return self.feat_prop2(adj_refined, feat, plan=plan, rows=plan.m_real)
 
 
+class _SeqEncoder(nn.Module):
+    """What the LSTM and GRU drop-ins share: ``self.rnn`` (torch's module of ``_rnn_class``, a holder of parameters only), the
+    reference's init of one layer and direction, and the layer loop of forward around the cell's own ``_layer``."""
+    _rnn_class = None
+
+    def __init__(self, input_size, hidden_size, batch_first, num_layers, bidirectional, dropout, reset_params=True):
+        super().__init__()
+        _drop_caches_on_load(self)
+        self.rnn = self._rnn_class(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers,
+                                   bidirectional=bidirectional, batch_first=batch_first)
+        if reset_params:
+            self.reset_params()
+        self.dropout = nn.Dropout(p=dropout)
+        self.last_seed = None       # input-dropout seed of the last training-mode forward (ops.feat_dropout)
+
+    def _suffixes(self):
+        return ("", "_reverse") if self.rnn.bidirectional else ("",)
+
+    def _param(self, kind, i, sfx):
+        return getattr(self.rnn, "%s_l%s%s" % (kind, i, sfx))
+
+    def _reset_one(self, i, sfx):
+        nn.init.orthogonal_(self._param("weight_hh", i, sfx))
+        nn.init.kaiming_normal_(self._param("weight_ih", i, sfx))
+        nn.init.constant_(self._param("bias_hh", i, sfx), val=0)
+        nn.init.constant_(self._param("bias_ih", i, sfx), val=0)
+
+    def reset_params(self):
+        for i in range(self.rnn.num_layers):
+            for sfx in self._suffixes():
+                self._reset_one(i, sfx)
+
+    def _layer(self, i, inp, lens, order, T):
+        """Layer i on `inp`: the input projections of its directions and the cell's recurrence op.  Returns y and h_n."""
+        raise NotImplementedError
+
+    def forward(self, x, return_h=True, max_len=None):
+        inp, lens, order, T, d_new_indices = _rnn_inputs(self, self._rnn_class.__name__, x, max_len)
+        states = []
+        for i in range(self.rnn.num_layers):
+            inp, h_n = self._layer(i, inp, lens, order, T)
+            states.append(h_n)
+        return inp, _rnn_state(states, return_h, d_new_indices)
+
+
 # ------------------------------------------------------------------ Models/BiDAF/wrapper.py:229-276
-class LSTM(nn.Module):
+class LSTM(_SeqEncoder):
     """The reference's LSTM sequence encoder on the HIP recurrence kernels (ops.lstm_seq).  ``self.rnn`` only holds the
     parameters (state_dict keys ``rnn.weight_ih_l0`` ...): it is never called, neither MIOpen nor nn.LSTM.forward runs.
 
@@ -244,40 +289,20 @@ class LSTM(nn.Module):
     dropout between layers (the reference passes none to nn.LSTM).  ``batch_first`` is accepted and irrelevant, as in the
     reference, whose forward hard-codes batch-first packing."""
 
+    _rnn_class = nn.LSTM
+
     def __init__(self, input_size, hidden_size, batch_first=False, num_layers=1, bidirectional=False, dropout=0.2,
                  _reset_params=True):
-        super().__init__()
-        _drop_caches_on_load(self)
-        self.rnn = nn.LSTM(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers,
-                           bidirectional=bidirectional, batch_first=batch_first)
-        if _reset_params:       # (Graph_basedSemantiStructure keeps nn.LSTM's own init: its seeded construction must not move)
-            self.reset_params()
-        self.dropout = nn.Dropout(p=dropout)
-        self.last_seed = None       # input-dropout seed of the last training-mode forward (ops.feat_dropout)
+        # (Graph_basedSemantiStructure keeps nn.LSTM's own init: its seeded construction must not move)
+        super().__init__(input_size, hidden_size, batch_first, num_layers, bidirectional, dropout, _reset_params)
 
-    def _suffixes(self):
-        return ("", "_reverse") if self.rnn.bidirectional else ("",)
-
-    def reset_params(self):
-        for i in range(self.rnn.num_layers):
-            for sfx in self._suffixes():
-                nn.init.orthogonal_(getattr(self.rnn, "weight_hh_l%s%s" % (i, sfx)))
-                nn.init.kaiming_normal_(getattr(self.rnn, "weight_ih_l%s%s" % (i, sfx)))
-                nn.init.constant_(getattr(self.rnn, "bias_hh_l%s%s" % (i, sfx)), val=0)
-                nn.init.constant_(getattr(self.rnn, "bias_ih_l%s%s" % (i, sfx)), val=0)
-
-    def forward(self, x, return_h=True, max_len=None):
-        inp, lens, order, T, d_new_indices = _rnn_inputs(self, "LSTM", x, max_len)
-        states = []
-        for i in range(self.rnn.num_layers):
-            gx, w_hh = [], []
-            for sfx in self._suffixes():
-                bias = getattr(self.rnn, "bias_ih_l%s%s" % (i, sfx)) + getattr(self.rnn, "bias_hh_l%s%s" % (i, sfx))
-                gx.append(ops.linear(inp, getattr(self.rnn, "weight_ih_l%s%s" % (i, sfx)), bias))
-                w_hh.append(getattr(self.rnn, "weight_hh_l%s%s" % (i, sfx)))
-            inp, h_n, _ = ops.lstm_seq(gx, w_hh, lens, order, T)
-            states.append(h_n)
-        return inp, _rnn_state(states, return_h, d_new_indices)
+    def _layer(self, i, inp, lens, order, T):
+        gx, w_hh = [], []
+        for sfx in self._suffixes():
+            bias = self._param("bias_ih", i, sfx) + self._param("bias_hh", i, sfx)
+            gx.append(ops.linear(inp, self._param("weight_ih", i, sfx), bias))
+            w_hh.append(self._param("weight_hh", i, sfx))
+        return ops.lstm_seq(gx, w_hh, lens, order, T)[:2]
 
 
 def _rnn_inputs(module, who, x, max_len):
@@ -311,7 +336,7 @@ def _rnn_state(states, return_h, d_new_indices):
 
 
 # ------------------------------------------------------------------ Models/BiDAF/wrapper.py:279-327
-class GRU(nn.Module):
+class GRU(_SeqEncoder):
     """The reference's GRU sequence encoder on the HIP recurrence kernels (ops.gru_seq).  ``self.rnn`` only holds the
     parameters (state_dict keys ``rnn.weight_ih_l0`` ...): it is never called, neither MIOpen nor nn.GRU.forward runs.
 
@@ -327,41 +352,24 @@ class GRU(nn.Module):
     state), d_new_indices used only as tiling order, outputs in the rows of x, y (B,T,dirs*H) zero at t >= len, h as there.
     Training mode: input dropout by ops.feat_dropout with its seed kept in ``last_seed``; no dropout between layers."""
 
+    _rnn_class = nn.GRU
+
     def __init__(self, input_size, hidden_size, batch_first=False, num_layers=1, bidirectional=False, dropout=0.2):
-        super().__init__()
-        _drop_caches_on_load(self)
-        self.rnn = nn.GRU(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers,
-                          bidirectional=bidirectional, batch_first=batch_first)
-        self.reset_params()
-        self.dropout = nn.Dropout(p=dropout)
-        self.last_seed = None       # input-dropout seed of the last training-mode forward (ops.feat_dropout)
+        super().__init__(input_size, hidden_size, batch_first, num_layers, bidirectional, dropout)
 
-    def _suffixes(self):
-        return ("", "_reverse") if self.rnn.bidirectional else ("",)
-
-    def reset_params(self):
+    def _reset_one(self, i, sfx):
         # wrapper.py:291-304, statement by statement, under no_grad (the fill_ of a view of a leaf raises otherwise)
         with torch.no_grad():
-            for i in range(self.rnn.num_layers):
-                for sfx in self._suffixes():
-                    nn.init.orthogonal_(getattr(self.rnn, "weight_hh_l%s%s" % (i, sfx)))
-                    nn.init.kaiming_normal_(getattr(self.rnn, "weight_ih_l%s%s" % (i, sfx)))
-                    nn.init.constant_(getattr(self.rnn, "bias_hh_l%s%s" % (i, sfx)), val=0)
-                    nn.init.constant_(getattr(self.rnn, "bias_ih_l%s%s" % (i, sfx)), val=0)
-                    getattr(self.rnn, "bias_hh_l%s%s" % (i, sfx)).chunk(4)[1].fill_(1)
+            super()._reset_one(i, sfx)
+            self._param("bias_hh", i, sfx).chunk(4)[1].fill_(1)
 
-    def forward(self, x, return_h=True, max_len=None):
-        inp, lens, order, T, d_new_indices = _rnn_inputs(self, "GRU", x, max_len)
-        states = []
-        for i in range(self.rnn.num_layers):
-            gx, w_hh, b_hh = [], [], []
-            for sfx in self._suffixes():
-                gx.append(ops.linear(inp, getattr(self.rnn, "weight_ih_l%s%s" % (i, sfx)), getattr(self.rnn, "bias_ih_l%s%s" % (i, sfx))))
-                w_hh.append(getattr(self.rnn, "weight_hh_l%s%s" % (i, sfx)))
-                b_hh.append(getattr(self.rnn, "bias_hh_l%s%s" % (i, sfx)))
-            inp, h_n = ops.gru_seq(gx, w_hh, b_hh, lens, order, T)
-            states.append(h_n)
-        return inp, _rnn_state(states, return_h, d_new_indices)
+    def _layer(self, i, inp, lens, order, T):
+        gx, w_hh, b_hh = [], [], []
+        for sfx in self._suffixes():
+            gx.append(ops.linear(inp, self._param("weight_ih", i, sfx), self._param("bias_ih", i, sfx)))
+            w_hh.append(self._param("weight_hh", i, sfx))
+            b_hh.append(self._param("bias_hh", i, sfx))
+        return ops.gru_seq(gx, w_hh, b_hh, lens, order, T)
 
 
 # ------------------------------------------------------------------ Models/BiDAF/wrapper.py:7-67

@@ -943,6 +943,55 @@ def add_layernorm(x, res, weight, bias, eps: float = 1e-5):
     return _AddLayerNorm.apply(x, res, weight, bias, eps)
 
 
+# --------------------------------------------------------------------------- what the two recurrences share
+def _rnn_args(who, G, gx0, gx1, w0, w1, lens, order, bias=False, b0=None, b1=None):
+    """Shapes and dtypes of one layer's operands (G gates; bias: the cell has recurrent biases b0 / b1 of its own), then the
+    fp32 contiguous tensors the kernels read: (n, t_in, h, dirs), gx pair, detached w_hh pair, detached b_hh pair, lens, order."""
+    dirs = 1 if gx1 is None else 2
+    shapes = "%s: gx (N,T,%dH), w_hh (%dH,H)%s per direction" % (who, G, G, ", b_hh (%dH,)" % G if bias else "")
+    assert gx0.dim() == 3 and w0.dim() == 2 and (w1 is None) == (gx1 is None) and (b0 is not None) == bias and \
+        (b1 is None) == (gx1 is None or not bias), shapes
+    n, t_in, hg = gx0.shape
+    h = w0.shape[1]
+    assert hg == G * h and w0.shape[0] == hg and (b0 is None or b0.shape == (hg,)) and \
+        (dirs == 1 or (gx1.shape == gx0.shape and w1.shape == w0.shape and (b0 is None or b1.shape == b0.shape))), shapes
+    assert lens.dtype == torch.int32 and lens.shape == (n,) and (order is None or (order.dtype == torch.int32 and order.shape == (n,))), \
+        who + ": lens and order are int32 (N,)"
+    f32 = lambda t: _f32(t) if t is not None else None
+    const = lambda t: _f32(t.detach()) if t is not None else None
+    return (n, t_in, h, dirs), (f32(gx0), f32(gx1)), (const(w0), const(w1)), (const(b0), const(b1)), lens.contiguous(), \
+        (order.contiguous() if order is not None else None)
+
+
+def _rnn_alloc(dev, dims, t_out, G, save):
+    """y (N,t_out,dirs*H), h_n (dirs,N,H) and, when a gradient is wanted, the saved gates (dirs,N,T_in,G*H), the cell's own
+    saved row and h_prev (dirs,N,T_in,H each)."""
+    n, t_in, h, dirs = dims
+    new = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
+    saved = (new(dirs, n, t_in, G * h), new(dirs, n, t_in, h), new(dirs, n, t_in, h)) if save else (None, None, None)
+    return new(n, t_out, dirs * h), new(dirs, n, h), saved
+
+
+def _rnn_wgrad(hprev, dpre, G, pw, pb, need_w, need_b):
+    """dW_hh = dpre^T h_prev (and db_hh = colsum(dpre) for a cell with a recurrent bias pb) of one direction: ONE call of the
+    weight-gradient GEMM (gh_linear_bwd without dx), straight into the parameters' .grad where _direct allows it for every
+    wanted gradient.  Returns what autograd still has to add: (dw, db), None where nothing is left."""
+    if not (need_w or need_b):
+        return None, None
+    _lib.ensure_workspace(dpre.device)
+    h = hprev.shape[-1]
+    direct = need_w and _direct(pw) and (pb is None or (need_b and _direct(pb)))
+    if direct:
+        dw, db = pw.grad, (pb.grad if pb is not None else None)
+    else:
+        dw = torch.zeros((G * h, h), device=dpre.device, dtype=torch.float32)
+        db = torch.zeros((G * h,), device=dpre.device, dtype=torch.float32) if pb is not None else None
+    call("gh_linear_bwd", ptr(hprev), None, None, ptr(dpre), hprev.shape[0] * hprev.shape[1], h, G * h, None, ptr(dw), ptr(db), stream())
+    if direct:
+        return None, None
+    return (dw if need_w else None), (db if need_b else None)
+
+
 # --------------------------------------------------------------------------- LSTM recurrence (wrapper.py:256-276)
 class _LstmSeq(torch.autograd.Function):
     """One layer's recurrence, both directions in one launch: csrc/rnn_ops.hip gh_lstm_seq_*.  The weight gradient
@@ -951,29 +1000,11 @@ class _LstmSeq(torch.autograd.Function):
     @staticmethod
     def forward(ctx, gx0, gx1, w0, w1, lens, order, t_out):
         _lib.require_cuda(gx0, gx1, w0, w1, lens, order)
-        dirs = 1 if gx1 is None else 2
-        assert gx0.dim() == 3 and w0.dim() == 2 and (w1 is None) == (gx1 is None), "lstm_seq: gx (N,T,4H), w_hh (4H,H) per direction"
-        n, t_in, h4 = gx0.shape
-        h = w0.shape[1]
-        assert h4 == 4 * h and w0.shape[0] == h4 and (dirs == 1 or (gx1.shape == gx0.shape and w1.shape == w0.shape)), \
-            "lstm_seq: gx (N,T,4H), w_hh (4H,H) per direction"
-        assert lens.dtype == torch.int32 and lens.shape == (n,) and (order is None or (order.dtype == torch.int32 and order.shape == (n,))), \
-            "lstm_seq: lens and order are int32 (N,)"
-        gx0 = _f32(gx0)
-        gx1 = _f32(gx1) if gx1 is not None else None
-        wc0 = _f32(w0.detach())
-        wc1 = _f32(w1.detach()) if w1 is not None else None
-        lens, order = lens.contiguous(), (order.contiguous() if order is not None else None)
-        dev = gx0.device
-        y = torch.empty((n, t_out, dirs * h), device=dev, dtype=torch.float32)
-        hn = torch.empty((dirs, n, h), device=dev, dtype=torch.float32)
+        dims, (gx0, gx1), (wc0, wc1), _, lens, order = _rnn_args("lstm_seq", 4, gx0, gx1, w0, w1, lens, order)
+        n, t_in, h, dirs = dims
+        y, hn, (gates, cs, hprev) = _rnn_alloc(gx0.device, dims, t_out, 4, any(ctx.needs_input_grad[:4]))
         cn = torch.empty_like(hn)
-        gates = cs = hprev = None
-        if any(ctx.needs_input_grad[:4]):
-            gates = torch.empty((dirs, n, t_in, h4), device=dev, dtype=torch.float32)
-            cs = torch.empty((dirs, n, t_in, h), device=dev, dtype=torch.float32)
-            hprev = torch.empty((dirs, n, t_in, h), device=dev, dtype=torch.float32)
-        call("gh_lstm_seq_fwd", ptr(gx0), ptr(gx1), h4, ptr(wc0), ptr(wc1), ptr(lens), ptr(order), n, t_in, t_out, h, dirs, ptr(y),
+        call("gh_lstm_seq_fwd", ptr(gx0), ptr(gx1), 4 * h, ptr(wc0), ptr(wc1), ptr(lens), ptr(order), n, t_in, t_out, h, dirs, ptr(y),
              dirs * h, ptr(gates), ptr(cs), ptr(hprev), ptr(hn), ptr(cn), stream())
         ctx.dims = (n, t_in, t_out, h, dirs)
         ctx.params = (w0, w1)
@@ -993,14 +1024,7 @@ class _LstmSeq(torch.autograd.Function):
              ptr(gates), ptr(cs), ptr(dgates), stream())
         dws = [None, None]
         for d in range(dirs):
-            if not ctx.needs_input_grad[2 + d]:
-                continue
-            _lib.ensure_workspace(dgates.device)
-            pw = ctx.params[d]
-            direct = _direct(pw)
-            dw = pw.grad if direct else torch.zeros((4 * h, h), device=dgates.device, dtype=torch.float32)
-            call("gh_linear_bwd", ptr(hprev[d]), None, None, ptr(dgates[d]), n * t_in, h, 4 * h, None, ptr(dw), None, stream())
-            dws[d] = None if direct else dw
+            dws[d], _ = _rnn_wgrad(hprev[d], dgates[d], 4, ctx.params[d], None, ctx.needs_input_grad[2 + d], False)
         return dgates[0], (dgates[1] if dirs == 2 else None), dws[0], dws[1], None, None, None
 
 
@@ -1024,30 +1048,10 @@ class _GruSeq(torch.autograd.Function):
     @staticmethod
     def forward(ctx, gx0, gx1, w0, w1, b0, b1, lens, order, t_out):
         _lib.require_cuda(gx0, gx1, w0, w1, b0, b1, lens, order)
-        dirs = 1 if gx1 is None else 2
-        shapes = "gru_seq: gx (N,T,3H), w_hh (3H,H), b_hh (3H,) per direction"
-        assert gx0.dim() == 3 and w0.dim() == 2 and b0 is not None and (w1 is None) == (gx1 is None) and (b1 is None) == (gx1 is None), shapes
-        n, t_in, h3 = gx0.shape
-        h = w0.shape[1]
-        assert h3 == 3 * h and w0.shape[0] == h3 and b0.shape == (h3,) and \
-            (dirs == 1 or (gx1.shape == gx0.shape and w1.shape == w0.shape and b1.shape == b0.shape)), shapes
-        assert lens.dtype == torch.int32 and lens.shape == (n,) and (order is None or (order.dtype == torch.int32 and order.shape == (n,))), \
-            "gru_seq: lens and order are int32 (N,)"
-        gx0 = _f32(gx0)
-        gx1 = _f32(gx1) if gx1 is not None else None
-        wc0, bc0 = _f32(w0.detach()), _f32(b0.detach())
-        wc1 = _f32(w1.detach()) if w1 is not None else None
-        bc1 = _f32(b1.detach()) if b1 is not None else None
-        lens, order = lens.contiguous(), (order.contiguous() if order is not None else None)
-        dev = gx0.device
-        y = torch.empty((n, t_out, dirs * h), device=dev, dtype=torch.float32)
-        hn = torch.empty((dirs, n, h), device=dev, dtype=torch.float32)
-        gates = an = hprev = None
-        if any(ctx.needs_input_grad[:6]):
-            gates = torch.empty((dirs, n, t_in, h3), device=dev, dtype=torch.float32)
-            an = torch.empty((dirs, n, t_in, h), device=dev, dtype=torch.float32)
-            hprev = torch.empty((dirs, n, t_in, h), device=dev, dtype=torch.float32)
-        call("gh_gru_seq_fwd", ptr(gx0), ptr(gx1), h3, ptr(wc0), ptr(wc1), ptr(bc0), ptr(bc1), ptr(lens), ptr(order), n, t_in, t_out, h,
+        dims, (gx0, gx1), (wc0, wc1), (bc0, bc1), lens, order = _rnn_args("gru_seq", 3, gx0, gx1, w0, w1, lens, order, True, b0, b1)
+        n, t_in, h, dirs = dims
+        y, hn, (gates, an, hprev) = _rnn_alloc(gx0.device, dims, t_out, 3, any(ctx.needs_input_grad[:6]))
+        call("gh_gru_seq_fwd", ptr(gx0), ptr(gx1), 3 * h, ptr(wc0), ptr(wc1), ptr(bc0), ptr(bc1), ptr(lens), ptr(order), n, t_in, t_out, h,
              dirs, ptr(y), dirs * h, ptr(gates), ptr(an), ptr(hprev), ptr(hn), stream())
         ctx.dims = (n, t_in, t_out, h, dirs)
         ctx.params = (w0, w1, b0, b1)
@@ -1066,20 +1070,8 @@ class _GruSeq(torch.autograd.Function):
              ptr(gates), ptr(an), ptr(hprev), ptr(dgx), ptr(da), stream())
         dws, dbs = [None, None], [None, None]
         for d in range(dirs):
-            need_w, need_b = ctx.needs_input_grad[2 + d], ctx.needs_input_grad[4 + d]
-            if not (need_w or need_b):
-                continue
-            _lib.ensure_workspace(da.device)
-            pw, pb = ctx.params[d], ctx.params[2 + d]
-            direct = need_w and need_b and _direct(pw) and _direct(pb)
-            if direct:
-                dw, db = pw.grad, pb.grad
-            else:
-                dw = torch.zeros((3 * h, h), device=da.device, dtype=torch.float32)
-                db = torch.zeros((3 * h,), device=da.device, dtype=torch.float32)
-            call("gh_linear_bwd", ptr(hprev[d]), None, None, ptr(da[d]), n * t_in, h, 3 * h, None, ptr(dw), ptr(db), stream())
-            if not direct:
-                dws[d], dbs[d] = (dw if need_w else None), (db if need_b else None)
+            dws[d], dbs[d] = _rnn_wgrad(hprev[d], da[d], 3, ctx.params[d], ctx.params[2 + d], ctx.needs_input_grad[2 + d],
+                                        ctx.needs_input_grad[4 + d])
         return dgx[0], (dgx[1] if dirs == 2 else None), dws[0], dws[1], dbs[0], dbs[1], None, None, None
 
 

@@ -1,10 +1,10 @@
 """Plain-torch restatement (tests only) of Models/BiDAF/bidaf_model.py: the attention-flow layer in closed form (no q_len
-loop, no squeeze), the highway layer and the whole model, with tests/lstm_ref.py for the two encoders.  Evaluated in float64
+loop, no squeeze), the highway layer and the whole model, with tests/rnn_ref.py for the two encoders.  Evaluated in float64
 by the GPU tests (tests/test_gpu_bidaf.py) and checked on its own against the reference's goldens by
 tests/test_bidaf_cpu.py."""
 import torch
 
-from tests.lstm_ref import lstm64
+from tests.rnn_ref import lstm64
 
 
 def att_flow64(c, q, w_c, w_q, w_cq, bias=0.0):

@@ -1,146 +1,29 @@
-"""CPU-side checks of the GRU sequence encoder (Models/BiDAF/wrapper.py:279-327): the float64 restatement the GPU tests
-compare the kernels with (tests/gru_ref.py) reproduces the reference's goldens on its own, the drop-in's constructor builds
-the reference's state_dict for every configuration in tests/golden/gru_contract.json and initialises a stand-alone module
-as the reference's constructor does once its one raising line runs, the C-ABI declares and binds the two recurrence entries,
-the shim exports the class, and the module refuses CPU tensors."""
-import os
-import re
-
-import numpy as np
+"""The CPU-side checks of the GRU encoder under the test ids this file always had.  The checks themselves live once, for both
+cells, in tests/test_rnn_cpu.py."""
 import pytest
-import torch
 
-from tests.gru_ref import gru64
-from tests.util import golden_ratio, load_golden, run_in_fresh_interpreter
+from tests import test_rnn_cpu as rnn
+from tests.rnn_ref import CELLS
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CASES = ["bi_b5", "bi_b5_max25", "uni_h5", "two_layers", "bi_b37", "bi_l70", "bi_b5_saturated"]
-
-
-def _archive(golden_dir):
-    return load_golden(golden_dir, "g16_gru.npz", "gru_contract.json")
-
-
-def _params(z, name):
-    key = f"{name}::param::"
-    return {k[len(key):]: torch.from_numpy(z[k]) for k in z if k.startswith(key)}
+CELL = CELLS["gru"]
 
 
 def test_gru_golden_archive_is_complete(golden_dir):
-    z, meta, contract = _archive(golden_dir)
-    assert meta["cases"] == CASES and set(contract) == set(CASES)
-    for name in CASES:
-        have = {k[len(name) + 2:] for k in z if k.startswith(name + "::")}
-        assert {"x", "lens", "new_indices", "restoring_indices", "y", "h", "gy", "gh", "grad::x"} <= have, name
-        names = [k for k, _ in contract[name]["state_dict"]]
-        assert {k[len("param::"):] for k in have if k.startswith("param::")} == set(names)
-        assert all("grad::" + k in have for k in names)
-        new, rest = z[name + "::new_indices"], z[name + "::restoring_indices"]
-        assert (new[rest] == np.arange(len(new))).all()                      # inverse permutations
-        assert (np.diff(z[name + "::lens"][new]) <= 0).all()                 # sorted by descending length
-        for k in names:                                                       # biases non-zero and distinct
-            if "bias_ih" in k:
-                bi, bh = z[f"{name}::param::{k}"], z[f"{name}::param::{k.replace('bias_ih', 'bias_hh')}"]
-                assert (bi != 0).all() and (bh != 0).all() and (bi != bh).all()
-    assert list(z["bi_b5::lens"]) == [21, 9, 9, 1, 14] and z["bi_b5_max25::y"].shape == (5, 25, 16)
-    assert (z["bi_b5_max25::y"][:, 21:] == 0).all()
-    assert np.array_equal(z["bi_b5_saturated::x"], np.float32(30.0) * z["bi_b5::x"])
-    assert "bi_b37::h_raw" in z and z["bi_b37::h_raw"].shape == (2, 37, 12)
-    assert os.path.getsize(os.path.join(golden_dir, "g16_gru.npz")) < 300 * 1024
+    rnn.test_golden_archive_is_complete(golden_dir, CELL)
 
 
-@pytest.mark.parametrize("name", CASES)
+@pytest.mark.parametrize("name", rnn.CASES)
 def test_float64_restatement_reproduces_the_gru_goldens(golden_dir, name):
-    """tests/gru_ref.py alone, in float64 on the archive's inputs and parameters: y, h and every gradient within
-    1e-5 + 1e-4 |want| of the reference's fp32 results."""
-    z, _, contract = _archive(golden_dir)
-    c = contract[name]
-    p64 = {k: v.double().requires_grad_(True) for k, v in _params(z, name).items()}
-    x = torch.from_numpy(z[name + "::x"]).double().requires_grad_(True)
-    lens = torch.from_numpy(z[name + "::lens"])
-    T = c["max_len"] or int(lens.max())
-    y, h = gru64(p64, x, lens, T, c["kwargs"].get("num_layers", 1), c["kwargs"].get("bidirectional", False))
-    ((y * torch.from_numpy(z[name + "::gy"]).double()).sum() + (h * torch.from_numpy(z[name + "::gh"]).double()).sum()).backward()
-    worst = 0.0
-    for k, got in [("y", y), ("h", h), ("grad::x", x.grad)] + [("grad::" + k, v.grad) for k, v in p64.items()]:
-        worst = max(worst, golden_ratio(got, z[f"{name}::{k}"], 1e-5, 1e-4, f"{name}::{k}"))
-    if name == "bi_b37":      # the raw second value of return_h=False: (layers * dirs, B, H) in the sorted order
-        raw = h.detach().view(37, 2, 12).permute(1, 0, 2)[:, torch.from_numpy(z[name + "::new_indices"])]
-        worst = max(worst, golden_ratio(raw, z[name + "::h_raw"], 1e-5, 1e-4, name + "::h_raw"))
-    print(f"{name}: worst ratio of the bound {worst:.3f}")
-    # padding: exact zeros in y and in the gradient of x at t >= len
-    dead = torch.arange(y.shape[1])[None, :] >= lens[:, None]
-    assert bool((y.detach()[dead] == 0).all()) and bool((x.grad[dead[:, :x.shape[1]]] == 0).all())
+    rnn.test_float64_restatement_reproduces_the_goldens(golden_dir, CELL, name)
 
 
 def test_gru_state_dicts_match_the_reference_contract(golden_dir):
-    from get_amd import modules
-    z, _, contract = _archive(golden_dir)
-    for name, c in contract.items():
-        m = modules.GRU(**c["kwargs"])
-        assert [[k, list(v.shape)] for k, v in m.state_dict().items()] == c["state_dict"], name
-        m.load_state_dict({"rnn." + k if not k.startswith("rnn.") else k: v for k, v in _params(z, name).items()}, strict=True)
-        assert torch.equal(m.rnn.weight_hh_l0, torch.from_numpy(z[name + "::param::rnn.weight_hh_l0"]))
-    assert [k for k, _ in contract["bi_b5"]["state_dict"]] == [
-        "rnn.weight_ih_l0", "rnn.weight_hh_l0", "rnn.bias_ih_l0", "rnn.bias_hh_l0",
-        "rnn.weight_ih_l0_reverse", "rnn.weight_hh_l0_reverse", "rnn.bias_ih_l0_reverse", "rnn.bias_hh_l0_reverse"]
-
-
-def test_stand_alone_gru_initialises_as_described():
-    """reset_params (wrapper.py:291-304 under no_grad): zero bias_ih, weight_hh with orthonormal columns, bias_hh equal to 1
-    exactly on chunk(4)[1] of the 3H-vector -- elements [ceil(3H/4), 2 ceil(3H/4)), straddling the r and z thirds -- and 0
-    elsewhere, per layer and direction."""
-    from get_amd import modules
-    torch.manual_seed(3)
-    for H in (8, 5):       # 3H = 24: pieces of 6; 3H = 15: pieces of 4, 4, 4, 3
-        m = modules.GRU(12, H, num_layers=2, bidirectional=True)
-        q = -(-3 * H // 4)
-        seen = 0
-        for k, p in m.named_parameters():
-            assert p.requires_grad and p.is_leaf, k
-            if "bias_ih" in k:
-                assert bool((p == 0).all()), k
-            elif "bias_hh" in k:
-                want = torch.zeros(3 * H)
-                want[q:2 * q] = 1
-                assert torch.equal(p.detach(), want), k
-                assert q < H < 2 * q      # the ones straddle the r and z thirds
-                seen += 1
-            elif "weight_hh" in k:
-                w = p.detach().double()
-                assert float((w.t() @ w - torch.eye(H, dtype=torch.float64)).abs().max()) <= 1e-5, k
-                seen += 1
-        assert seen == 8 and isinstance(m.dropout, torch.nn.Dropout) and m.dropout.p == 0.2 and m.last_seed is None
-        assert isinstance(m.rnn, torch.nn.GRU)
+    rnn.test_state_dicts_match_the_reference_contract(golden_dir, CELL)
 
 
 def test_header_declares_and_binding_matches_the_gru_entries():
-    from get_amd import _lib
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "get_hip.h")).read(), flags=re.S)
-    for name in ("gh_gru_seq_fwd", "gh_gru_seq_bwd"):
-        m = re.search(r"\bint\s+%s\s*\(([^;]*?)\)\s*;" % name, src, flags=re.S)
-        assert m, f"{name} is not declared in include/get_hip.h"
-        nargs = len([a for a in m.group(1).split(",") if a.strip()])
-        assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name]) == nargs, name
-    assert "#define GH_ABI_VERSION 10" in src and _lib.ABI_VERSION == 10
-
-
-def test_install_serves_the_gru_import_path(tmp_path):
-    run_in_fresh_interpreter(tmp_path, "from Models.BiDAF.wrapper import GRU, LSTM\n"
-                             "assert GRU is M.GRU and GRU.__module__ == 'get_amd.modules' and LSTM is M.LSTM",
-                             packages=("Models", "Models/BiDAF"))
+    rnn.test_header_declares_and_binding_matches_the_entries(CELL)
 
 
 def test_gru_refuses_cpu_tensors_and_bad_lengths():
-    from get_amd import modules, ops
-    m = modules.GRU(6, 4, bidirectional=True).eval()
-    x, idx = torch.zeros(2, 5, 6), torch.arange(2)
-    with pytest.raises(RuntimeError, match="no CPU path"):
-        m((x, torch.tensor([5, 3]), idx, idx), max_len=5)
-    with pytest.raises(RuntimeError, match="no CPU path"):
-        ops.gru_seq([torch.zeros(2, 5, 12)], [torch.zeros(12, 4)], [torch.zeros(12)], torch.ones(2, dtype=torch.int32), None, 5)
-    # host lengths outside [1, T] raise as the reference's pack / pad functions do
-    with pytest.raises(ValueError):
-        m((x, torch.tensor([5, 0]), idx, idx), max_len=5)
-    with pytest.raises(ValueError):
-        m((x, torch.tensor([5, 3]), idx, idx), max_len=4)
+    rnn.test_refuses_cpu_tensors_and_bad_lengths(CELL)
