@@ -66,6 +66,16 @@ SIGNATURES = {
                         _P, _P],
     "gh_highway_fwd": [_P, _P, _P, _I, _I, _P, _P],
     "gh_highway_bwd": [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
+    "gh_soft_align_fwd": [_P, _P, _P, _I, _I, _I, _P, _P, _F, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P],
+    "gh_soft_align_bwd": [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _I, _P],
+    "gh_lin_att_fwd": [_P, _P, _I, _I, _I, _I, _P, _P],
+    "gh_lin_att_bwd": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "gh_match_dot_fwd": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "gh_match_dot_bwd": [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "gh_match_bcast_fwd": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
+    "gh_match_bcast_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "gh_gauss_kernel_fwd": [_P, _F, _F, _L, _P, _P],
+    "gh_gauss_kernel_bwd": [_P, _P, _P, _F, _F, _L, _P, _P],
     "gh_evd_assemble_fwd": [_P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "gh_evd_assemble_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "gh_clamp_events": [_P, _I],

@@ -39,4 +39,9 @@ def install():
     # the sequence-matching baseline built from wrapper.LSTM / wrapper.Linear
     _module("Models.BiDAF.bidaf_model", BiDAF=M.BiDAF, LSTM=M.LSTM, Linear=M.Linear, KeyWordSettings=KeyWordSettings,
             torch=torch, nn=nn, np=np)
+    # the parts sequence-matching baselines are assembled from (basic_fc_model.py:6 imports GaussianKernel from here).
+    # BertModule is not served: it needs the vendored pytorch_transformers, and importing it raises ImportError
+    _module("matchzoo.modules", Attention=M.Attention, BidirectionalAttention=M.BidirectionalAttention,
+            MatchModule=M.MatchModule, RNNDropout=M.RNNDropout, StackedBRNN=M.StackedBRNN, GaussianKernel=M.GaussianKernel,
+            Matching=M.Matching, torch=torch, nn=nn)
     return M

@@ -13,6 +13,8 @@ load unchanged:
                                                MultiHeadSelfAttentionICLR17OnWord, SelfAttentionType
   Models/FCWithEvidences/graph_based_semantic_structure.py   Graph_basedSemantiStructure
   Models/BiDAF/bidaf_model.py                  BiDAF
+  matchzoo/modules                             Attention, BidirectionalAttention, MatchModule, Matching, GaussianKernel,
+                                               RNNDropout, StackedBRNN
 
 Adjacency arguments may be the reference's dense ``(N,R,R)`` tensors (any float dtype; packed once
 on the device, values kept exactly) or a native :class:`get_amd.ops.PackedAdj` from
@@ -297,12 +299,28 @@ class LSTM(_SeqEncoder):
         super().__init__(input_size, hidden_size, batch_first, num_layers, bidirectional, dropout, _reset_params)
 
     def _layer(self, i, inp, lens, order, T):
-        gx, w_hh = [], []
-        for sfx in self._suffixes():
-            bias = self._param("bias_ih", i, sfx) + self._param("bias_hh", i, sfx)
-            gx.append(ops.linear(inp, self._param("weight_ih", i, sfx), bias))
-            w_hh.append(self._param("weight_hh", i, sfx))
-        return ops.lstm_seq(gx, w_hh, lens, order, T)[:2]
+        return _lstm_layer(lambda kind, sfx: self._param(kind, i, sfx), self._suffixes(), inp, lens, order, T)
+
+
+def _lstm_layer(param, suffixes, inp, lens, order, T):
+    """One LSTM layer on `inp` (B,L,D): the input projection of each direction (ops.linear, both biases folded into it) and the
+    recurrence (ops.lstm_seq).  param(kind, suffix) gives the layer's parameters.  Returns y (B,T,dirs*H) and h_n."""
+    gx, w_hh = [], []
+    for sfx in suffixes:
+        bias = param("bias_ih", sfx) + param("bias_hh", sfx)
+        gx.append(ops.linear(inp, param("weight_ih", sfx), bias))
+        w_hh.append(param("weight_hh", sfx))
+    return ops.lstm_seq(gx, w_hh, lens, order, T)[:2]
+
+
+def _gru_layer(param, suffixes, inp, lens, order, T):
+    """One GRU layer on `inp`: as _lstm_layer, with b_hh staying with the recurrence (ops.gru_seq)."""
+    gx, w_hh, b_hh = [], [], []
+    for sfx in suffixes:
+        gx.append(ops.linear(inp, param("weight_ih", sfx), param("bias_ih", sfx)))
+        w_hh.append(param("weight_hh", sfx))
+        b_hh.append(param("bias_hh", sfx))
+    return ops.gru_seq(gx, w_hh, b_hh, lens, order, T)
 
 
 def _rnn_inputs(module, who, x, max_len):
@@ -364,12 +382,7 @@ class GRU(_SeqEncoder):
             self._param("bias_hh", i, sfx).chunk(4)[1].fill_(1)
 
     def _layer(self, i, inp, lens, order, T):
-        gx, w_hh, b_hh = [], [], []
-        for sfx in self._suffixes():
-            gx.append(ops.linear(inp, self._param("weight_ih", i, sfx), self._param("bias_ih", i, sfx)))
-            w_hh.append(self._param("weight_hh", i, sfx))
-            b_hh.append(self._param("bias_hh", i, sfx))
-        return ops.gru_seq(gx, w_hh, b_hh, lens, order, T)
+        return _gru_layer(lambda kind, sfx: self._param(kind, i, sfx), self._suffixes(), inp, lens, order, T)
 
 
 # ------------------------------------------------------------------ Models/BiDAF/wrapper.py:7-67
@@ -1054,3 +1067,172 @@ class BiDAF(nn.Module):
                    query_lens_indices=lens_indices(kargs[KeyWordSettings.Query_lens]),
                    doc_lens_indices=lens_indices(kargs[KeyWordSettings.Doc_lens]))
         return out.detach().cpu().numpy().flatten()
+
+
+# ------------------------------------------------------------------ matchzoo/modules/attention.py:9-38
+class Attention(nn.Module):
+    """softmax(linear(x)) over the kept positions (ops.lin_att): x (B,L,input_size) -> (B,L).  ``mask`` is the reference's
+    integer, read as its two comparisons read it -- ``mask = (s != m)`` and ``masked_fill(mask == m, -inf)`` on the scores s:
+    m == 0 (the default) excludes the positions that score exactly 0 (all-zero rows of x), m == 1 excludes every position that
+    does not score exactly 1, and any other m excludes nothing.  A sequence without a kept position is NaN in its own row."""
+
+    def __init__(self, input_size: int = 100, mask: int = 0):
+        super().__init__()
+        self.linear = nn.Linear(input_size, 1, bias=False)
+        self.mask = mask
+
+    def forward(self, x):
+        mode = 0 if self.mask == 0 else (1 if self.mask == 1 else 2)
+        return ops.lin_att(x, self.linear.weight, mode)
+
+
+# ------------------------------------------------------------------ matchzoo/modules/attention.py:41-65
+class BidirectionalAttention(nn.Module):
+    """Soft attention between two sequences, both ways (ops.soft_align twice): forward(v1 (B,L1,D), v1_mask (B,L1), v2
+    (B,L2,D), v2_mask (B,L2)) -> attended_v1 (B,L1,D), attended_v2 (B,L2,D).  The masks are bool, True = padding (any other
+    dtype raises RuntimeError, as torch's masked_fill does).  As in the reference a padded key is NOT excluded: its score is
+    replaced by -1e-7 and it keeps a weight; only the padded ROWS of the two results are zeroed."""
+
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, v1, v1_mask, v2, v2_mask):
+        for m in (v1_mask, v2_mask):
+            if m.dtype != torch.bool:
+                raise RuntimeError(f"BidirectionalAttention: masked_fill only supports boolean masks, but got mask with dtype {m.dtype}")
+        attended_v1 = ops.soft_align(v1, v2, v2, v2_mask, row_zero=v1_mask)[0]
+        # the reference's softmax(dim=1) branch, transposed
+        attended_v2 = ops.soft_align(v2, v1, v1, v1_mask, row_zero=v2_mask)[0]
+        return attended_v1, attended_v2
+
+
+# ------------------------------------------------------------------ matchzoo/modules/attention.py:68-107
+class MatchModule(nn.Module):
+    """The match representation of Match-LSTM: forward(v1 (B,L1,H), v2 (B,L2,H), v2_mask (B,L2), any dtype, nonzero =
+    padding) -> (B,L1,2H) = dropout(relu(proj([v1, o, v1 - o, v1 * o]))), o = softmax(fill(v1 v2_proj(v2)^T)) v2.  The
+    alignment and the four-way cat are one kernel (ops.soft_align with fuse); padded keys keep a weight (score -1e-7), as in
+    the reference.  Training mode with dropout_rate > 0: the stateless mask of ops.feat_dropout, seed kept in ``last_seed``."""
+
+    def __init__(self, hidden_size, dropout_rate=0):
+        super().__init__()
+        _drop_caches_on_load(self)
+        self.v2_proj = nn.Linear(hidden_size, hidden_size)
+        self.proj = nn.Linear(hidden_size * 4, hidden_size * 2)
+        self.dropout = nn.Dropout(p=dropout_rate)
+        self.last_seed = None
+
+    def forward(self, v1, v2, v2_mask):
+        _lib.require_cuda(v1, v2, v2_mask)
+        proj_v2 = ops.linear(v2, self.v2_proj.weight, self.v2_proj.bias)
+        fusion = ops.soft_align(v1, proj_v2, v2, v2_mask != 0, fuse=True)[0]
+        match = ops.relu(ops.linear(fusion, self.proj.weight, self.proj.bias))
+        p, seed = _encoder_drop(self.training, self.dropout.p)
+        self.last_seed = seed if p > 0 else None
+        return ops.feat_dropout(match, p, seed)
+
+
+# ------------------------------------------------------------------ matchzoo/modules/matching.py:9-61
+class Matching(nn.Module):
+    """The matching matrix between two sequences: forward(x (B,L,D), y (B,R,D)) -> (B,L,R) for 'dot' (ops.match_dot; the
+    cosine with normalize, where a row with a norm <= 1e-12 gets gradients of the order 1e12, as F.normalize gives), and
+    (B,L,R,D) for 'mul', 'plus', 'minus', (B,L,R,2D) for 'concat' (ops.match_bcast)."""
+
+    def __init__(self, normalize: bool = False, matching_type: str = 'dot'):
+        super().__init__()
+        self._normalize = normalize
+        self._validate_matching_type(matching_type)
+        self._matching_type = matching_type
+
+    @classmethod
+    def _validate_matching_type(cls, matching_type: str = 'dot'):
+        valid_matching_type = ['dot', 'mul', 'plus', 'minus', 'concat']
+        if matching_type not in valid_matching_type:
+            raise ValueError("%s is not a valid matching type, %s expected." % (matching_type, valid_matching_type))
+
+    def forward(self, x, y):
+        if self._matching_type == 'dot':
+            return ops.match_dot(x, y, self._normalize)
+        return ops.match_bcast(x, y, self._matching_type)
+
+
+# ------------------------------------------------------------------ matchzoo/modules/gaussian_kernel.py:8-36
+class GaussianKernel(nn.Module):
+    """exp(-0.5 (x - mu)^2 / sigma^2), elementwise (ops.gauss_kernel); sigma == 0 raises at the first forward."""
+
+    def __init__(self, mu: float = 1., sigma: float = 1.):
+        super().__init__()
+        self.mu = mu
+        self.sigma = sigma
+
+    def forward(self, x):
+        return ops.gauss_kernel(x, self.mu, self.sigma)
+
+
+# ------------------------------------------------------------------ matchzoo/modules/dropout.py:4-18
+class RNNDropout(nn.Dropout):
+    """Dropout of whole feature columns of a sequence batch: forward(x (B,L,D)).  Eval mode returns the input.  Training mode
+    draws ONE (B,D) mask, shared by all L positions and scaled by 1 / (1 - p), with the stateless hash of ops.feat_dropout on
+    a tensor of ones; its seed is kept in ``last_seed``, so ops.dropout_mask_reference(seed, B, D, p) replays it."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.last_seed = None
+
+    def forward(self, sequences_batch):
+        p, seed = _encoder_drop(self.training, self.p)
+        self.last_seed = seed if p > 0 else None
+        if p <= 0:
+            return sequences_batch
+        _lib.require_cuda(sequences_batch)
+        ones = sequences_batch.new_ones((sequences_batch.shape[0], sequences_batch.shape[-1]), dtype=torch.float32)
+        return ops.feat_dropout(ones, p, seed).unsqueeze(1) * sequences_batch
+
+
+# ------------------------------------------------------------------ matchzoo/modules/stacked_brnn.py:6-91
+class StackedBRNN(nn.Module):
+    """Stacked bidirectional LSTM / GRU layers with the option to concatenate the layers' outputs, on the HIP recurrence
+    kernels.  ``self.rnns`` holds one ``rnn_type(in, hidden, num_layers=1, bidirectional=True)`` per layer as a holder of
+    parameters (state_dict keys ``rnns.{i}.weight_ih_l0`` ..., drawn as the reference draws them); the holders are never
+    called.  rnn_type is nn.LSTM or nn.GRU, anything else raises TypeError.
+
+    forward(x (B,L,D), x_mask) -> (B,L,2H), or (B,L,layers*2H) with concat_layers.  Every sequence runs over its full length
+    L: the reference's _forward_unpadded ignores the padding, and so does this; x_mask is accepted and NOT read (the
+    reference's ``x_mask.data.sum() == 0`` is a host synchronisation whose result it discards).  Each layer is the input
+    projection (ops.linear) and the recurrence (ops.lstm_seq / ops.gru_seq) of modules.LSTM / modules.GRU, whose limits apply.
+    Training mode with dropout_rate > 0: ops.feat_dropout on every layer's input, seeds kept in ``last_seeds`` (one per
+    layer), and with dropout_output on the result, seed kept in ``last_output_seed``."""
+
+    def __init__(self, input_size, hidden_size, num_layers, dropout_rate=0, dropout_output=False, rnn_type=nn.LSTM,
+                 concat_layers=False):
+        super().__init__()
+        if rnn_type not in (nn.LSTM, nn.GRU):
+            raise TypeError("StackedBRNN: rnn_type must be nn.LSTM or nn.GRU, got %r" % (rnn_type,))
+        _drop_caches_on_load(self)
+        self.dropout_output = dropout_output
+        self.dropout_rate = dropout_rate
+        self.num_layers = num_layers
+        self.concat_layers = concat_layers
+        self.rnns = nn.ModuleList()
+        for i in range(num_layers):
+            input_size = input_size if i == 0 else 2 * hidden_size
+            self.rnns.append(rnn_type(input_size, hidden_size, num_layers=1, bidirectional=True))
+        self._layer_fn = _lstm_layer if rnn_type is nn.LSTM else _gru_layer
+        self.last_seeds = [None] * num_layers
+        self.last_output_seed = None
+
+    def forward(self, x, x_mask=None):
+        _lib.require_cuda(x)
+        assert x.dim() == 3, "StackedBRNN: x is (B, L, D)"
+        B, L = x.shape[0], x.shape[1]
+        lens = torch.full((B,), L, device=x.device, dtype=torch.int32)
+        outputs, inp = [], x
+        for i, rnn in enumerate(self.rnns):
+            p, seed = _encoder_drop(self.training, self.dropout_rate)
+            self.last_seeds[i] = seed if p > 0 else None
+            inp = ops.feat_dropout(inp, p, seed)
+            inp = self._layer_fn(lambda kind, sfx: getattr(rnn, "%s_l0%s" % (kind, sfx)), ("", "_reverse"), inp, lens, None, L)[0]
+            outputs.append(inp)
+        output = torch.cat(outputs, 2) if self.concat_layers else outputs[-1]
+        p, seed = _encoder_drop(self.training and self.dropout_output, self.dropout_rate)
+        self.last_output_seed = seed if p > 0 else None
+        return ops.feat_dropout(output, p, seed).contiguous()

@@ -522,6 +522,67 @@ int gh_highway_fwd(const float* x, const float* h_pre, const float* g_pre, int r
 int gh_highway_bwd(const float* x, const float* h_pre, const float* g_pre, const float* g, int rows, int d, float* dh_pre,
                    float* dg_pre, float* dx, gh_stream_t stream);
 
+/* ---- the matchzoo/modules family (get_amd/csrc/match_ops.hip) ----
+ * Soft alignment between two sequences, replacing matchzoo/modules/attention.py:50-63 (BidirectionalAttention: the bmm, both
+ * masked_fill + softmax, both bmm and both masked_fill_) and :99-105 (MatchModule: the bmm, masked_fill, softmax, bmm and the
+ * four-way cat).
+ *   q [b][lq][d] (ldq), k [b][lk][d] (ldk), v [b][lk][dv] (ldv): read in place, e.g. column slices.
+ *   key_fill [b][lk] uint8, nonzero = filled; row_zero [b][lq] uint8 or NULL; fill finite (a non-finite one is rejected).
+ *   S_ij = q_i.k_j, then S_ij = fill where key_fill_j: the score is REPLACED by the constant and KEEPS its weight -- the
+ *   reference's masked_fill(mask, -1e-7) as written, not an exclusion.  A = softmax_j(S) (running maximum subtracted),
+ *   a [b][lq][lk] is always written; a sequence whose keys are all filled gets uniform weights 1 / lk, never NaN.
+ *   o_i = sum_j A_ij v_j, then o_i = 0 where row_zero_i.
+ *   fuse == 0: out [b][lq][dv] (ldo) = o.   fuse == 1 (needs dv == d, row_zero == NULL): out [b][lq][4d] = [q, o, q - o, q * o].
+ * Limits: lq, lk <= 1024, d, dv <= 2048, b * ceil(max(lq, lk) / 16) < 2^31; anything beyond them is rejected with an error and
+ * nothing is written.  Nothing is allocated.  No atomics: two runs are bit-identical. */
+int gh_soft_align_fwd(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const uint8_t* key_fill,
+                      const uint8_t* row_zero /*NULL ok*/, float fill, int fuse, int b, int lq, int lk, int d, int dv, float* a,
+                      float* out, int ldo, gh_stream_t stream);
+/* Backward of the above from g (ldg; [b][lq][dv], or [b][lq][4d] with slices g0 .. g3 when fuse):
+ *   g_o = g, or g1 - g2 + g3 * q with fuse; g_o = 0 in the rows of row_zero
+ *   dv_j = sum_i A_ij g_o,i (filled keys DO receive it);  dA_ij = g_o,i.v_j;  dS = A (dA - sum_j A dA), then dS_ij = 0 where
+ *   key_fill_j (the fill is a constant);  dq_i = sum_j dS_ij k_j (+ g0 + g2 + g3 * o with fuse, o re-read from out);
+ *   dk_j = sum_i dS_ij q_i.
+ * ds [b][lq][lk] is scratch of the caller's; out is only read with fuse.  Every element of dq, dk and dvv is written. */
+int gh_soft_align_bwd(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const uint8_t* key_fill,
+                      const uint8_t* row_zero /*NULL ok*/, int fuse, const float* a, const float* out /*fuse only*/, int ldo,
+                      const float* g, int ldg, int b, int lq, int lk, int d, int dv, float* ds /*scratch*/, float* dq, int lddq,
+                      float* dk, int lddk, float* dvv, int lddv, gh_stream_t stream);
+/* matchzoo/modules/attention.py:35-38 (Attention): s_l = x_l.w (x [b][l][d] contiguous, w [d], no bias), position l is excluded
+ * according to mode -- the reference's mask = (x != m); masked_fill(mask == m, -inf) read literally: mode 0 (m == 0) excludes
+ * s_l == 0, mode 1 (m == 1) excludes s_l != 1, mode 2 (any other m) excludes nothing -- and a [b][l] = the softmax over the
+ * kept positions, exactly 0 at the excluded ones.  A sequence without a kept position is NaN in its own row, as in the
+ * reference.  s_l is formed from products only, so an all-zero row scores exactly 0.  Limits: l <= 4096, d <= 2048. */
+int gh_lin_att_fwd(const float* x, const float* w, int mode, int b, int l, int d, float* a, gh_stream_t stream);
+/* Backward from g [b][l]: ds_l = a_l (g_l - sum_l a_l g_l), dx_l = ds_l w, dw = sum over the sequences of sum_l ds_l x_l:
+ * part [b][d] (scratch of the caller's) holds the per-sequence sums, added in sequence order into dw (written, not +=). */
+int gh_lin_att_bwd(const float* x, const float* w, const float* a, const float* g, int b, int l, int d, float* dx,
+                   float* part /*scratch*/, float* dw, gh_stream_t stream);
+/* matchzoo/modules/matching.py:46-50: out [b][l][r] = x_l.y_r (x [b][l][d] ldx, y [b][r][d] ldy); with normalize times
+ * ix_l iy_r, i = 1 / max(||row||_2, 1e-12) (F.normalize), ix [b][l] and iy [b][r] written and saved.
+ * Limits: l, r <= 1024, d <= 2048. */
+int gh_match_dot_fwd(const float* x, const float* y, int ldx, int ldy, int normalize, int b, int l, int r, int d,
+                     float* ix /*normalize only*/, float* iy /*normalize only*/, float* out, gh_stream_t stream);
+/* Backward from g [b][l][r]: gs = g * ix * iy, dx_raw = gs y, dy_raw = gs^T x (dx [b][l][d], dy [b][r][d] contiguous).  With
+ * normalize a row above the clamp gets dx = dx_raw - x (x.dx_raw) ix^2; a row with ||x|| <= 1e-12 keeps dx_raw (the gradient of
+ * clamp_min is zero there), which is of the order 1e12 g, exactly as torch gives. */
+int gh_match_dot_bwd(const float* x, const float* y, int ldx, int ldy, int normalize, const float* ix, const float* iy,
+                     const float* g, int b, int l, int r, int d, float* dx, float* dy, gh_stream_t stream);
+/* matchzoo/modules/matching.py:52-61: out [b][l][r][d] = x_l op y_r for op 0 mul, 1 plus, 2 minus; op 3 concat writes
+ * [b][l][r][2d] = [x_l, y_r].  Written once from x [b][l][d] and y [b][r][d] (contiguous), without the reference's two repeat
+ * copies.  64-bit offsets.  Limit: d <= 2048. */
+int gh_match_bcast_fwd(const float* x, const float* y, int op, int b, int l, int r, int d, float* out, gh_stream_t stream);
+/* Backward: dx_l = sum_r (g * y | g | g | g[:d]), dy_r = sum_l (g * x | g | -g | g[d:]); one owner per output element and a
+ * fixed summation order. */
+int gh_match_bcast_bwd(const float* x, const float* y, const float* g, int op, int b, int l, int r, int d, float* dx,
+                       float* dy, gh_stream_t stream);
+/* matchzoo/modules/gaussian_kernel.py:34-36: y = exp(-0.5 (x - mu)^2 / sigma^2) over n elements (y == x is fine);
+ * sigma == 0 is rejected. */
+int gh_gauss_kernel_fwd(const float* x, float mu, float sigma, long long n, float* y, gh_stream_t stream);
+/* dx = -g y (x - mu) / sigma^2 from the saved y. */
+int gh_gauss_kernel_bwd(const float* x, const float* y, const float* g, float mu, float sigma, long long n, float* dx,
+                        gh_stream_t stream);
+
 /* ---- a8  ragged helpers: Models/FCWithEvidences/basic_fc_model.py:80-121 ----
  * offsets[b+1] int32 prefix sum of evidence counts (device). */
 /* has[b] (NULL ok) = 1.0 for claims with at least one evidence: row 0 of pad_right(x) is x's first row of the claim times has. */
