@@ -5,11 +5,8 @@
 // There is NO mask, as in the reference: c and q are LSTM outputs with exact-zero rows at t >= len, and those rows take part
 // in both softmaxes (a zero row of q scores c_i.w_c + bias, a zero row of c scores q_j.w_q + bias).
 //
-// The products run on v_mfma_f32_16x16x4_f32 (exact fp32) from operands staged in LDS, with the layouts of mha_ops.hip:
-//   KC  element (i, k) at i * pitch + k, pitch % 8 == 4    (reduction index contiguous)
-//   KM  element (k, j) at k * pitch + j, pitch % 32 == 16  (reduction index is the row)
-// Rows are zero-filled to a multiple of 16 and the depth to a multiple of 4, so one code path serves every lc, lq and d; a
-// staging load moves 16 bytes per lane where the source rows are 16-byte aligned and whole, and single floats elsewhere.
+// The products run on the MFMA from operands staged in LDS: the KC / KM layouts, the staging and the MFMA helpers are those of
+// score_tile.hip.h, which mha_ops.hip and match_ops.hip use as well.
 // The width d is walked in blocks of AF_BLK = 640 columns (10 accumulators per wave; the project's 600 is one block).
 //
 //   forward, tiles     one workgroup per (batch element, 16 context rows).  The left operand is c_i * w_cq + w_q, so that one
@@ -24,11 +21,11 @@
 //   backward, keys     one workgroup per (batch element, 16 query rows) walks the context rows: dq = a^T dc2q + colsum(dS)
 //                      w_q + w_cq * (dS^T c), and the per-tile partials of dw_q and dw_cq.
 //   sums               the partials on the stream workspace, added to dw_c / dw_q / dw_cq in a fixed order.
-// Every output element has one owner, there are no atomics: two runs are bit-identical.  (The few staging and MFMA helpers
-// repeat those of mha_ops.hip with this file's block width; sharing them would mean touching that file's kernels.)
+// Every output element has one owner, there are no atomics: two runs are bit-identical.
 #include "../../include/get_hip.h"
 #include "common.h"
 #include "device_utils.h"
+#include "score_tile.hip.h"
 #include <math.h>
 
 namespace gh {
@@ -36,6 +33,7 @@ namespace {
 
 constexpr int AF_THREADS = 256;
 constexpr int AF_WAVES = AF_THREADS / 64;
+static_assert(AF_THREADS == TILE_THREADS, "score_tile.hip.h strides its loops by its own workgroup size");
 constexpr int AF_MAX_LC = 1024;          // beta of one batch element in LDS; dA / dS tile [16][lq]
 constexpr int AF_MAX_LQ = 1024;          // one 16-row score tile [16][lq] in LDS (64 KB at the limit)
 constexpr int AF_MAX_D = 2048;           // dq2c of one batch element in LDS
@@ -43,75 +41,19 @@ constexpr int AF_BLK = 640;              // columns of one depth / column block
 constexpr int AF_NT = AF_BLK / 16 / AF_WAVES;      // column tiles per wave: 10 accumulators
 constexpr int AF_CHUNK = 16 * 656;       // floats of one staged operand chunk (41 KB): 16 rows at the widest pitch (656)
 
-__host__ __device__ inline int af_pitch_km(int n) { n = up16(n); return (n & 31) == 16 ? n : n + 16; }
-__host__ __device__ inline int af_min(int a, int b) { return a < b ? a : b; }
-// rows of a chunk with `pitch` floats per row: a multiple of 16, at least 16, at most the padded extent
-__host__ __device__ inline int af_chunk_rows(int extent, int pitch, int budget) {
-  int r = (budget / pitch) & ~15;
-  if (r < 16) r = 16;
-  const int e = up16(extent);
-  return r < e ? r : e;
-}
-
 // LDS of the two row-tiled kernels: left [16][pa] | ss [16][ps] | chunk | 16 row scalars
-struct TilePlan { int pa, ps, pk, pv, kc1, kc2, chunk; };
-__host__ __device__ inline TilePlan tile_plan(int lq, int d) {
-  TilePlan p;
-  p.pa = pitch_kc(af_min(up4(d), AF_BLK));
-  p.ps = pitch_kc(up16(lq));
-  p.pk = p.pa;
-  p.pv = af_pitch_km(af_min(up16(d), AF_BLK));
-  p.kc1 = af_chunk_rows(lq, p.pk, AF_CHUNK);
-  p.kc2 = af_chunk_rows(lq, p.pv, AF_CHUNK);
-  const int c1 = p.kc1 * p.pk, c2 = p.kc2 * p.pv;
-  p.chunk = c1 > c2 ? c1 : c2;
-  return p;
-}
+__host__ __device__ inline TilePlan af_plan(int lq, int d) { return tile_plan<AF_BLK, AF_CHUNK>(lq, d); }
 __host__ __device__ inline int tile_lds_floats(const TilePlan& p) { return 16 * p.pa + 16 * p.ps + p.chunk + 16; }
 
 // LDS of the key-tiled kernel: cc [rc][pm] | gc [rc][pm] | dst [rc][16] | wt [rc][16] | 16 column sums
 struct KeyPlan { int pm, rc; };
 __host__ __device__ inline KeyPlan key_plan(int lc, int d) {
   KeyPlan p;
-  p.pm = af_pitch_km(af_min(up16(d), AF_BLK));
-  p.rc = af_chunk_rows(lc, 2 * p.pm, AF_CHUNK);
+  p.pm = pitch_km(imin(up16(d), AF_BLK));
+  p.rc = chunk_rows(lc, 2 * p.pm, AF_CHUNK);
   return p;
 }
 __host__ __device__ inline int key_lds_floats(const KeyPlan& p) { return p.rc * (2 * p.pm + 32) + 16; }
-
-__device__ __forceinline__ bool vec_ok(const float* p, long long ld) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (ld & 3) == 0; }
-
-// four floats from p (the first `n` of them exist), 16 bytes at once where `vec`
-__device__ __forceinline__ float4 ld4(const float* __restrict__ p, bool vec, int n) {
-  if (vec && n >= 4) return *reinterpret_cast<const float4*>(p);
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  v.x = p[0];
-  if (n > 1) v.y = p[1];
-  if (n > 2) v.z = p[2];
-  if (n > 3) v.w = p[3];
-  return v;
-}
-
-// LDS [rows_pad][pitch] <- f(r, c) for r < rows, c < cols in steps of four columns, zero elsewhere; cols_pad % 4 == 0.
-// f returns the four values of columns c .. c + 3 and must itself return zeros for the columns >= cols: every f below builds
-// its result from ld4, which zero-fills.
-template <class F>
-__device__ __forceinline__ void stage_f(float* dst, int pitch, int rows_pad, int cols_pad, int rows, int cols, F f) {
-  const int c4n = cols_pad >> 2;
-  for (int idx = threadIdx.x; idx < rows_pad * c4n; idx += AF_THREADS) {
-    const int r = idx / c4n, c = (idx - r * c4n) << 2;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < rows && c < cols) v = f(r, c);
-    *reinterpret_cast<float4*>(dst + r * pitch + c) = v;
-  }
-}
-
-// rows x cols of a row-major source -> LDS [rows_pad][pitch], zero-filled beyond (rows, cols)
-__device__ __forceinline__ void stage(float* dst, int pitch, int rows_pad, int cols_pad, const float* __restrict__ src, long long ld,
-                                      int rows, int cols) {
-  const bool vec = vec_ok(src, ld);
-  stage_f(dst, pitch, rows_pad, cols_pad, rows, cols, [=](int r, int c) { return ld4(src + (size_t)r * ld + c, vec, cols - c); });
-}
 
 // g1 + g2 * c (the gradient that reaches c2q), columns k0 .. k0 + cols of rows row0 .. of one batch element
 __device__ __forceinline__ void stage_dc2q(float* dst, int pitch, int rows_pad, int cols_pad, const float* __restrict__ g, long long ldg,
@@ -127,85 +69,6 @@ __device__ __forceinline__ void stage_dc2q(float* dst, int pitch, int rows_pad, 
   });
 }
 
-// LDS tile [16][pitch] (only the first `rows` rows and `cols` columns) -> row-major global, 16 bytes per lane where possible
-__device__ __forceinline__ void unstage(float* __restrict__ dst, long long ld, const float* src, int pitch, int rows, int cols) {
-  if (vec_ok(dst, ld) && (cols & 3) == 0) {
-    const int c4n = cols >> 2;
-    for (int idx = threadIdx.x; idx < rows * c4n; idx += AF_THREADS) {
-      const int r = idx / c4n, c = (idx - r * c4n) << 2;
-      *reinterpret_cast<float4*>(dst + (size_t)r * ld + c) = *reinterpret_cast<const float4*>(src + r * pitch + c);
-    }
-  } else {
-    for (int idx = threadIdx.x; idx < rows * cols; idx += AF_THREADS) {
-      const int r = idx / cols, c = idx - r * cols;
-      dst[(size_t)r * ld + c] = src[r * pitch + c];
-    }
-  }
-}
-
-// S[16][key0 + ...] (+)= X Y^T for a chunk: X = xs [16][px] (KC), Y = ys [rows_pad][py] (KC), depth % 4 == 0.  Wave w owns the
-// 16-column tiles w, w + 4, ... in every call, so `accumulate` re-reads what the same lane wrote for the previous depth block.
-// C/D map: column = lane & 15, row = 4 (lane >> 4) + r.
-__device__ __forceinline__ void mma_scores(const float* xs, int px, const float* ys, int py, int rows_pad, int depth, float* ss, int ps,
-                                           int key0, bool accumulate) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, qd = lane >> 4;
-  for (int jt = wave; jt < (rows_pad >> 4); jt += AF_WAVES) {
-    const float* xa = xs + l15 * px + qd;
-    const float* yb = ys + (jt * 16 + l15) * py + qd;
-    float* so = ss + (4 * qd) * ps + key0 + jt * 16 + l15;
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    if (accumulate) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc0[r] = so[r * ps];
-    }
-    int k0 = 0;
-    for (; k0 + 8 <= depth; k0 += 8) {      // two accumulators: the dependent-accumulator latency exceeds the issue interval
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[k0], yb[k0], acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[k0 + 4], yb[k0 + 4], acc1, 0, 0, 0);
-    }
-    if (k0 < depth) acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[k0], yb[k0], acc0, 0, 0, 0);
-    acc0 += acc1;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) so[r * ps] = acc0[r];
-  }
-}
-
-// acc[t] += A B for the column tiles ct = wave + 4 t < ntiles: A element (i, k) at as[i * sai + k * sak], B = bs [kk][pb] (KM)
-__device__ __forceinline__ void mma_acc(const float* as, int sai, int sak, const float* bs, int pb, int kk, int ntiles, f32x4* acc) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, qd = lane >> 4;
-  const float* ap = as + l15 * sai + qd * sak;
-  const float* bp = bs + qd * pb + wave * 16 + l15;
-  for (int k0 = 0; k0 < kk; k0 += 4) {
-    const float a = ap[k0 * sak];
-#pragma unroll
-    for (int t = 0; t < AF_NT; ++t)
-      if (wave + AF_WAVES * t < ntiles)
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp[k0 * pb + t * 16 * AF_WAVES], acc[t], 0, 0, 0);
-  }
-}
-
-// sum over the workgroup in a fixed order (lanes by butterfly, then the waves in order); every thread gets the result
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float s = 0.f;
-#pragma unroll
-  for (int w = 0; w < AF_WAVES; ++w) s += red[w];
-  return s;
-}
-__device__ __forceinline__ float block_max(float v, float* red) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float s = red[0];
-#pragma unroll
-  for (int w = 1; w < AF_WAVES; ++w) s = fmaxf(s, red[w]);
-  return s;
-}
-
 // ============================================================================ forward, row tiles
 // grid b * ceil(lc / 16).  LDS: as [16][pa] | ss [16][ps] | chunk | rs [16]
 __global__ __launch_bounds__(AF_THREADS) void
@@ -214,7 +77,7 @@ af_fwd_tile_kernel(const float* __restrict__ c, const float* __restrict__ q, lon
                    const float* __restrict__ b_q, const float* __restrict__ b_cq, int lc, int lq, int d, float* __restrict__ x,
                    long long ldx, float* __restrict__ a, int32_t* __restrict__ amax, float* __restrict__ m) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const TilePlan P = tile_plan(lq, d);
+  const TilePlan P = af_plan(lq, d);
   float* as = sm;
   float* ss = as + 16 * P.pa;
   float* ch = ss + 16 * P.ps;
@@ -307,7 +170,7 @@ af_fwd_tile_kernel(const float* __restrict__ c, const float* __restrict__ q, lon
       __syncthreads();
       stage(ch, P.pv, rp, up16(nb), qb + (size_t)key0 * ldq + c0, ldq, nk, nb);
       __syncthreads();
-      mma_acc(ss + key0, P.ps, 1, ch, P.pv, rp, nct, acc);
+      mma_acc<AF_NT>(ss + key0, P.ps, 1, ch, P.pv, rp, nct, acc);
     }
 #pragma unroll
     for (int t = 0; t < AF_NT; ++t) {
@@ -414,7 +277,7 @@ af_bwd_row_kernel(const float* __restrict__ c, const float* __restrict__ q, long
                   const float* __restrict__ g, long long ldg, const float* __restrict__ dm, const float* __restrict__ dq2c, int lc, int lq,
                   int d, float* __restrict__ ds, float* __restrict__ dc, long long lddc) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const TilePlan P = tile_plan(lq, d);
+  const TilePlan P = af_plan(lq, d);
   float* gs = sm;
   float* ss = gs + 16 * P.pa;
   float* ch = ss + 16 * P.ps;
@@ -474,7 +337,7 @@ af_bwd_row_kernel(const float* __restrict__ c, const float* __restrict__ q, long
       __syncthreads();
       stage(ch, P.pv, rp, up16(nb), qb + (size_t)key0 * ldq + c0, ldq, nk, nb);
       __syncthreads();
-      mma_acc(ss + key0, P.ps, 1, ch, P.pv, rp, nct, acc);
+      mma_acc<AF_NT>(ss + key0, P.ps, 1, ch, P.pv, rp, nct, acc);
     }
 #pragma unroll
     for (int t = 0; t < AF_NT; ++t) {
@@ -544,8 +407,8 @@ af_bwd_key_kernel(const float* __restrict__ c, const float* __restrict__ q, long
       stage(dst, 16, rp, 16, ds + sbase + (size_t)i0 * lq, lq, nr, nk);
       stage(wt, 16, rp, 16, a + sbase + (size_t)i0 * lq, lq, nr, nk);
       __syncthreads();
-      mma_acc(dst, 1, 16, cc, P.pm, rp, nct, accu);      // u = dS^T c
-      mma_acc(wt, 1, 16, gc, P.pm, rp, nct, accv);       // a^T dc2q
+      mma_acc<AF_NT>(dst, 1, 16, cc, P.pm, rp, nct, accu);      // u = dS^T c
+      mma_acc<AF_NT>(wt, 1, 16, gc, P.pm, rp, nct, accv);       // a^T dc2q
     }
     // (sd was written before the first barrier above and is only read from here on)
 #pragma unroll
@@ -685,7 +548,7 @@ extern "C" int gh_att_flow_fwd(const float* c, const float* q, int ldc, int ldq,
   if (int rc = af_check("att_flow_fwd", b, lc, lq, d)) return rc;
   GH_REQUIRE(c && q && w_c && w_q && w_cq && b_c && b_q && b_cq && x && a && amax && m && beta && q2c, "att_flow_fwd: NULL argument");
   GH_REQUIRE(ldc >= d && ldq >= d && (long long)ldx >= 4LL * d, "att_flow_fwd: a leading dimension is smaller than its row");
-  const size_t lds = (size_t)tile_lds_floats(tile_plan(lq, d)) * sizeof(float);
+  const size_t lds = (size_t)tile_lds_floats(af_plan(lq, d)) * sizeof(float);
   if (int rc = lds_opt_in(af_fwd_tile_kernel, lds, "att_flow_fwd")) return rc;
   hipLaunchKernelGGL(af_fwd_tile_kernel, dim3(b * ((lc + 15) / 16)), dim3(AF_THREADS), lds, st, c, q, (long long)ldc, (long long)ldq, w_c,
                      w_q, w_cq, b_c, b_q, b_cq, lc, lq, d, x, (long long)ldx, a, amax, m);
@@ -713,7 +576,7 @@ extern "C" int gh_att_flow_bwd(const float* c, const float* q, int ldc, int ldq,
              need);
   float* part_c = wsp.p;
   float* part_k = wsp.p + (size_t)b * d;
-  const size_t lds_r = (size_t)tile_lds_floats(tile_plan(lq, d)) * sizeof(float);
+  const size_t lds_r = (size_t)tile_lds_floats(af_plan(lq, d)) * sizeof(float);
   const size_t lds_k = (size_t)key_lds_floats(key_plan(lc, d)) * sizeof(float);
   if (int rc = lds_opt_in(af_bwd_row_kernel, lds_r, "att_flow_bwd")) return rc;
   if (int rc = lds_opt_in(af_bwd_key_kernel, lds_k, "att_flow_bwd")) return rc;

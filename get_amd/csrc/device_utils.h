@@ -1,6 +1,7 @@
-// Helpers shared by the drop-in kernel files (attention_ops.hip, encoder_ops.hip, mha_ops.hip, rnn_ops.hip): wave and
-// 16-lane reductions, round-up and LDS-pitch arithmetic, the alignment test of the float4 paths and the opt-in to more than
-// 64 KB of LDS.
+// Helpers shared by the drop-in kernel files (attention_ops.hip, encoder_ops.hip, mha_ops.hip, rnn_ops.hip, bidaf_ops.hip,
+// match_ops.hip): wave and 16-lane reductions, round-up and LDS-pitch arithmetic, the alignment test of the float4 paths and
+// the opt-in to more than 64 KB of LDS.  score_tile.hip.h builds on it: the LDS staging and MFMA helpers of the three files that
+// keep a 16-row score tile in LDS (mha_ops.hip, bidaf_ops.hip, match_ops.hip).
 #pragma once
 #include "common.h"
 

@@ -7,11 +7,8 @@
 //   gh_match_bcast_*   matching.py:52-61: x_l (* | + | - | cat) y_r written once, without the reference's two repeat copies
 //   gh_gauss_kernel_*  gaussian_kernel.py:34-36
 //
-// The products run on v_mfma_f32_16x16x4_f32 (exact fp32) from operands staged in LDS, with the layouts of mha_ops.hip:
-//   KC  element (i, k) at i * pitch + k, pitch % 8 == 4    (reduction index contiguous)
-//   KM  element (k, j) at k * pitch + j, pitch % 32 == 16  (reduction index is the row)
-// Rows are zero-filled to a multiple of 16 and the depth to a multiple of 4, so one code path serves every length and depth; a
-// staging load moves 16 bytes per lane where the source rows are 16-byte aligned and whole, and single floats elsewhere.
+// The products run on the MFMA from operands staged in LDS: the KC / KM layouts, the staging and the MFMA helpers are those of
+// score_tile.hip.h, which bidaf_ops.hip and mha_ops.hip use as well.
 // A width is walked in blocks of MT_BLK = 128 columns (two accumulators per wave; the project's 600 is five blocks): a narrow
 // block leaves room for operand chunks of 64 rows, so that all four waves own a score tile per chunk, and for three workgroups
 // per CU (53 KB of LDS at the project's shape), which overlap one another's staging and MFMA phases.
@@ -24,11 +21,11 @@
 //                          query rows: dk = dS^T q, dv = A^T g_o.
 //   match_dot              forward: the score tile of soft_align, scaled by the two inverse norms.  backward: one kernel, run
 //                          once per side, d_rows = (g * ix * iy) other, then the projection of F.normalize on its own rows.
-// Every output element has one owner, there are no atomics: two runs are bit-identical.  (The staging and MFMA helpers repeat
-// those of bidaf_ops.hip; sharing them would mean touching that file's kernels.)
+// Every output element has one owner, there are no atomics: two runs are bit-identical.
 #include "../../include/get_hip.h"
 #include "common.h"
 #include "device_utils.h"
+#include "score_tile.hip.h"
 #include <math.h>
 
 namespace gh {
@@ -36,6 +33,7 @@ namespace {
 
 constexpr int MT_THREADS = 256;
 constexpr int MT_WAVES = MT_THREADS / 64;
+static_assert(MT_THREADS == TILE_THREADS, "score_tile.hip.h strides its loops by its own workgroup size");
 constexpr int SA_MAX_L = 1024;           // one 16-row score tile [16][lk] in LDS (64 KB at the limit)
 constexpr int SA_MAX_D = 2048;
 constexpr int LA_MAX_L = 4096;           // the scores of one sequence in LDS
@@ -45,75 +43,19 @@ constexpr int MT_BLK = 128;
 constexpr int MT_NT = MT_BLK / 16 / MT_WAVES;      // column tiles per wave: 2 accumulators
 constexpr int MT_CHUNK = 16 * 656;       // floats of one staged operand chunk (41 KB): 64 rows at this block's pitches (132, 144)
 
-__host__ __device__ inline int mt_pitch_km(int n) { n = up16(n); return (n & 31) == 16 ? n : n + 16; }
-__host__ __device__ inline int mt_min(int a, int b) { return a < b ? a : b; }
-__host__ __device__ inline int mt_max(int a, int b) { return a > b ? a : b; }
-// rows of a chunk with `pitch` floats per row: a multiple of 16, at least 16, at most the padded extent
-__host__ __device__ inline int mt_chunk_rows(int extent, int pitch, int budget) {
-  int r = (budget / pitch) & ~15;
-  if (r < 16) r = 16;
-  const int e = up16(extent);
-  return r < e ? r : e;
-}
-
 // LDS of the row-tiled kernels: left [16][pa] | ss [16][ps] | chunk.  n = the length the scores run over, w = the widest depth
-struct TilePlan { int pa, ps, pk, pv, kc1, kc2, chunk; };
-__host__ __device__ inline TilePlan tile_plan(int n, int w) {
-  TilePlan p;
-  p.pa = pitch_kc(mt_min(up4(w), MT_BLK));
-  p.ps = pitch_kc(up16(n));
-  p.pk = p.pa;
-  p.pv = mt_pitch_km(mt_min(up16(w), MT_BLK));
-  p.kc1 = mt_chunk_rows(n, p.pk, MT_CHUNK);
-  p.kc2 = mt_chunk_rows(n, p.pv, MT_CHUNK);
-  const int c1 = p.kc1 * p.pk, c2 = p.kc2 * p.pv;
-  p.chunk = c1 > c2 ? c1 : c2;
-  return p;
-}
+__host__ __device__ inline TilePlan mt_plan(int n, int w) { return tile_plan<MT_BLK, MT_CHUNK>(n, w); }
 __host__ __device__ inline int tile_lds_floats(const TilePlan& p) { return 16 * p.pa + 16 * p.ps + p.chunk; }
 
 // LDS of the key-tiled kernel: mm [rc][pm] | st [rc][16]
 struct KeyPlan { int pm, rc; };
 __host__ __device__ inline KeyPlan key_plan(int n, int w) {
   KeyPlan p;
-  p.pm = mt_pitch_km(mt_min(up16(w), MT_BLK));
-  p.rc = mt_chunk_rows(n, p.pm + 16, MT_CHUNK);
+  p.pm = pitch_km(imin(up16(w), MT_BLK));
+  p.rc = chunk_rows(n, p.pm + 16, MT_CHUNK);
   return p;
 }
 __host__ __device__ inline int key_lds_floats(const KeyPlan& p) { return p.rc * (p.pm + 16); }
-
-__device__ __forceinline__ bool vec_ok(const float* p, long long ld) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (ld & 3) == 0; }
-
-// four floats from p (the first `n` of them exist), 16 bytes at once where `vec`
-__device__ __forceinline__ float4 ld4(const float* __restrict__ p, bool vec, int n) {
-  if (vec && n >= 4) return *reinterpret_cast<const float4*>(p);
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  v.x = p[0];
-  if (n > 1) v.y = p[1];
-  if (n > 2) v.z = p[2];
-  if (n > 3) v.w = p[3];
-  return v;
-}
-
-// LDS [rows_pad][pitch] <- f(r, c) for r < rows, c < cols in steps of four columns, zero elsewhere; cols_pad % 4 == 0.
-// f returns the four values of columns c .. c + 3 with zeros for the columns >= cols: every f below builds on ld4.
-template <class F>
-__device__ __forceinline__ void stage_f(float* dst, int pitch, int rows_pad, int cols_pad, int rows, int cols, F f) {
-  const int c4n = cols_pad >> 2;
-  for (int idx = threadIdx.x; idx < rows_pad * c4n; idx += MT_THREADS) {
-    const int r = idx / c4n, c = (idx - r * c4n) << 2;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < rows && c < cols) v = f(r, c);
-    *reinterpret_cast<float4*>(dst + r * pitch + c) = v;
-  }
-}
-
-// rows x cols of a row-major source -> LDS [rows_pad][pitch], zero-filled beyond (rows, cols)
-__device__ __forceinline__ void stage(float* dst, int pitch, int rows_pad, int cols_pad, const float* __restrict__ src, long long ld,
-                                      int rows, int cols) {
-  const bool vec = vec_ok(src, ld);
-  stage_f(dst, pitch, rows_pad, cols_pad, rows, cols, [=](int r, int c) { return ld4(src + (size_t)r * ld + c, vec, cols - c); });
-}
 
 // The gradient that reaches o, columns k0 .. k0 + cols of `rows` rows from the row the pointers stand on:
 //   fuse == 0   g, zero where rz (NULL ok) marks the row
@@ -143,111 +85,6 @@ __device__ __forceinline__ void stage_go(float* dst, int pitch, int rows_pad, in
   });
 }
 
-// LDS tile [16][pitch] (only the first `rows` rows and `cols` columns) -> row-major global, 16 bytes per lane where possible
-__device__ __forceinline__ void unstage(float* __restrict__ dst, long long ld, const float* src, int pitch, int rows, int cols) {
-  if (vec_ok(dst, ld) && (cols & 3) == 0) {
-    const int c4n = cols >> 2;
-    for (int idx = threadIdx.x; idx < rows * c4n; idx += MT_THREADS) {
-      const int r = idx / c4n, c = (idx - r * c4n) << 2;
-      *reinterpret_cast<float4*>(dst + (size_t)r * ld + c) = *reinterpret_cast<const float4*>(src + r * pitch + c);
-    }
-  } else {
-    for (int idx = threadIdx.x; idx < rows * cols; idx += MT_THREADS) {
-      const int r = idx / cols, c = idx - r * cols;
-      dst[(size_t)r * ld + c] = src[r * pitch + c];
-    }
-  }
-}
-
-// S[16][key0 + ...] (+)= X Y^T for a chunk: X = xs [16][px] (KC), Y = ys [rows_pad][py] (KC), depth % 4 == 0.  Wave w owns the
-// 16-column tiles w, w + 4, ... in every call, so `accumulate` re-reads what the same lane wrote for the previous depth block.
-// C/D map: column = lane & 15, row = 4 (lane >> 4) + r.
-__device__ __forceinline__ void mma_scores(const float* xs, int px, const float* ys, int py, int rows_pad, int depth, float* ss, int ps,
-                                           int key0, bool accumulate) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, qd = lane >> 4;
-  for (int jt = wave; jt < (rows_pad >> 4); jt += MT_WAVES) {
-    const float* xa = xs + l15 * px + qd;
-    const float* yb = ys + (jt * 16 + l15) * py + qd;
-    float* so = ss + (4 * qd) * ps + key0 + jt * 16 + l15;
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    if (accumulate) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc0[r] = so[r * ps];
-    }
-    int k0 = 0;
-    for (; k0 + 8 <= depth; k0 += 8) {      // two accumulators: the dependent-accumulator latency exceeds the issue interval
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[k0], yb[k0], acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[k0 + 4], yb[k0 + 4], acc1, 0, 0, 0);
-    }
-    if (k0 < depth) acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[k0], yb[k0], acc0, 0, 0, 0);
-    acc0 += acc1;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) so[r * ps] = acc0[r];
-  }
-}
-
-// acc[t] += A B for the column tiles ct = wave + 4 t < ntiles: A element (i, k) at as[i * sai + k * sak], B = bs [kk][pb] (KM)
-__device__ __forceinline__ void mma_acc(const float* as, int sai, int sak, const float* bs, int pb, int kk, int ntiles, f32x4* acc) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, qd = lane >> 4;
-  const float* ap = as + l15 * sai + qd * sak;
-  const float* bp = bs + qd * pb + wave * 16 + l15;
-  for (int k0 = 0; k0 < kk; k0 += 4) {
-    const float a = ap[k0 * sak];
-#pragma unroll
-    for (int t = 0; t < MT_NT; ++t)
-      if (wave + MT_WAVES * t < ntiles)
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp[k0 * pb + t * 16 * MT_WAVES], acc[t], 0, 0, 0);
-  }
-}
-
-// sum / maximum over the workgroup in a fixed order (lanes by butterfly, then the waves in order); every thread gets the result
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float s = 0.f;
-#pragma unroll
-  for (int w = 0; w < MT_WAVES; ++w) s += red[w];
-  return s;
-}
-__device__ __forceinline__ float block_max(float v, float* red) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float s = red[0];
-#pragma unroll
-  for (int w = 1; w < MT_WAVES; ++w) s = fmaxf(s, red[w]);
-  return s;
-}
-
-// ss [16][ps] (+)= xs ys^T with ys = the `n` rows of `src` (ld), columns k0 .. k0 + nb, walked in chunks of `kc` rows through ch
-__device__ __forceinline__ void scores_block(const float* xs, int px, float* ch, int pk, int kc, const float* __restrict__ src, long long ld,
-                                             int n, int k0, int nb, float* ss, int ps, bool accumulate) {
-  const int nb4 = up4(nb);
-  for (int key0 = 0; key0 < n; key0 += kc) {
-    const int nk = mt_min(kc, n - key0), rp = up16(nk);
-    __syncthreads();
-    stage(ch, pk, rp, nb4, src + (size_t)key0 * ld + k0, ld, nk, nb);
-    __syncthreads();
-    mma_scores(xs, px, ch, pk, rp, nb4, ss, ps, key0, accumulate);
-  }
-}
-
-// acc += ss[:, 0:n] B with B = the `n` rows of `src` (ld), columns c0 .. c0 + nb, walked in chunks of `kc` rows through ch
-__device__ __forceinline__ void weighted_block(const float* ss, int ps, float* ch, int pv, int kc, const float* __restrict__ src, long long ld,
-                                               int n, int c0, int nb, f32x4* acc) {
-  const int nct = (nb + 15) >> 4;
-  for (int key0 = 0; key0 < n; key0 += kc) {
-    const int nk = mt_min(kc, n - key0), rp = up4(nk);
-    __syncthreads();
-    stage(ch, pv, rp, up16(nb), src + (size_t)key0 * ld + c0, ld, nk, nb);
-    __syncthreads();
-    mma_acc(ss + key0, ps, 1, ch, pv, rp, nct, acc);
-  }
-}
-
 // ============================================================================ soft_align forward
 // grid b * ceil(lq / 16).  LDS: qs [16][pa] | ss [16][ps] | chunk
 __global__ __launch_bounds__(MT_THREADS) void
@@ -255,7 +92,7 @@ sa_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const fl
               long long ldv, const uint8_t* __restrict__ key_fill, const uint8_t* __restrict__ row_zero, float fill, int fuse, int lq,
               int lk, int d, int dv, float* __restrict__ a, float* __restrict__ out, long long ldo) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const TilePlan P = tile_plan(lk, mt_max(d, dv));
+  const TilePlan P = mt_plan(lk, imax(d, dv));
   float* qs = sm;
   float* ss = qs + 16 * P.pa;
   float* ch = ss + 16 * P.ps;
@@ -308,7 +145,7 @@ sa_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const fl
     f32x4 acc[MT_NT];
 #pragma unroll
     for (int t = 0; t < MT_NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    weighted_block(ss, P.ps, ch, P.pv, P.kc2, vb, ldv, lk, c0, nb, acc);
+    weighted_block<MT_NT>(ss, P.ps, ch, P.pv, P.kc2, vb, ldv, lk, c0, nb, acc);
 #pragma unroll
     for (int t = 0; t < MT_NT; ++t) {
       const int col = (wave + MT_WAVES * t) * 16 + l15;
@@ -343,7 +180,7 @@ sa_bwd_row_kernel(const float* __restrict__ q, const float* __restrict__ k, cons
                   const float* __restrict__ a, const float* __restrict__ out, long long ldo, const float* __restrict__ g, long long ldg,
                   int lq, int lk, int d, int dv, float* __restrict__ ds, float* __restrict__ dq, long long lddq) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const TilePlan P = tile_plan(lk, mt_max(d, dv));
+  const TilePlan P = mt_plan(lk, imax(d, dv));
   float* gs = sm;
   float* ss = gs + 16 * P.pa;
   float* ch = ss + 16 * P.ps;
@@ -390,7 +227,7 @@ sa_bwd_row_kernel(const float* __restrict__ q, const float* __restrict__ k, cons
     f32x4 acc[MT_NT];
 #pragma unroll
     for (int t = 0; t < MT_NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    weighted_block(ss, P.ps, ch, P.pv, P.kc2, kb, ldk, lk, c0, nb, acc);
+    weighted_block<MT_NT>(ss, P.ps, ch, P.pv, P.kc2, kb, ldk, lk, c0, nb, acc);
 #pragma unroll
     for (int t = 0; t < MT_NT; ++t) {
       const int col = (wave + MT_WAVES * t) * 16 + l15;
@@ -421,7 +258,7 @@ sa_bwd_key_kernel(const float* __restrict__ q, long long ldq, const uint8_t* __r
                   const float* __restrict__ ds, const float* __restrict__ g, long long ldg, int lq, int lk, int d, int dv,
                   float* __restrict__ dk, long long lddk, float* __restrict__ dvv, long long lddv) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const KeyPlan P = key_plan(lq, mt_max(d, dv));
+  const KeyPlan P = key_plan(lq, imax(d, dv));
   float* mm = sm;
   float* st = mm + P.rc * P.pm;
   const int nkt = (lk + 15) >> 4;
@@ -451,7 +288,7 @@ sa_bwd_key_kernel(const float* __restrict__ q, long long ldq, const uint8_t* __r
           stage(mm, P.pm, rp, up16(nb), q + (q0 + i0) * ldq + c0, ldq, nr, nb);
         stage(st, 16, rp, 16, tsrc + sbase + (size_t)i0 * lk, lk, nr, nk);
         __syncthreads();
-        mma_acc(st, 1, 16, mm, P.pm, rp, nct, acc);
+        mma_acc<MT_NT>(st, 1, 16, mm, P.pm, rp, nct, acc);
       }
 #pragma unroll
       for (int t = 0; t < MT_NT; ++t) {
@@ -561,7 +398,7 @@ __global__ __launch_bounds__(MT_THREADS) void
 md_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y, long long ldx, long long ldy, const float* __restrict__ ix,
               const float* __restrict__ iy, int l, int r, int d, float* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const TilePlan P = tile_plan(r, d);
+  const TilePlan P = mt_plan(r, d);
   float* xs = sm;
   float* ss = xs + 16 * P.pa;
   float* ch = ss + 16 * P.ps;
@@ -599,7 +436,7 @@ __global__ __launch_bounds__(MT_THREADS) void
 md_bwd_kernel(const float* __restrict__ s, const float* __restrict__ o, long long lds_, long long ldo_, const float* __restrict__ is,
               const float* __restrict__ io, const float* __restrict__ g, int ls, int lo, int d, float* __restrict__ ds_out) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const TilePlan P = tile_plan(lo, d);
+  const TilePlan P = mt_plan(lo, d);
   float* ss = sm;
   float* ch = ss + 16 * P.ps;
   const int nrt = (ls + 15) >> 4;
@@ -631,7 +468,7 @@ md_bwd_kernel(const float* __restrict__ s, const float* __restrict__ o, long lon
     f32x4 acc[MT_NT];
 #pragma unroll
     for (int t = 0; t < MT_NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    weighted_block(ss, P.ps, ch, P.pv, P.kc2, ob, ldo_, lo, c0, nb, acc);
+    weighted_block<MT_NT>(ss, P.ps, ch, P.pv, P.kc2, ob, ldo_, lo, c0, nb, acc);
 #pragma unroll
     for (int t = 0; t < MT_NT; ++t) {
       const int col = (wave + MT_WAVES * t) * 16 + l15;
@@ -784,7 +621,7 @@ extern "C" int gh_soft_align_fwd(const float* q, const float* k, const float* v,
   GH_REQUIRE(!fuse || (dv == d && !row_zero), "soft_align_fwd: fuse needs dv == d (got %d, %d) and no row_zero", dv, d);
   GH_REQUIRE(ldq >= d && ldk >= d && ldv >= dv && (long long)ldo >= (fuse ? 4LL * d : (long long)dv),
              "soft_align_fwd: a leading dimension is smaller than its row");
-  const size_t lds = (size_t)tile_lds_floats(tile_plan(lk, mt_max(d, dv))) * sizeof(float);
+  const size_t lds = (size_t)tile_lds_floats(mt_plan(lk, imax(d, dv))) * sizeof(float);
   if (int rc = lds_opt_in(sa_fwd_kernel, lds, "soft_align_fwd")) return rc;
   hipLaunchKernelGGL(sa_fwd_kernel, dim3(b * ((lq + 15) / 16)), dim3(MT_THREADS), lds, st, q, k, v, (long long)ldq, (long long)ldk,
                      (long long)ldv, key_fill, row_zero, fill, fuse, lq, lk, d, dv, a, out, (long long)ldo);
@@ -804,8 +641,8 @@ extern "C" int gh_soft_align_bwd(const float* q, const float* k, const float* v,
   const long long wo = fuse ? 4LL * d : (long long)dv;
   GH_REQUIRE(ldq >= d && ldk >= d && ldv >= dv && lddq >= d && lddk >= d && lddv >= dv && ldg >= wo && (!fuse || ldo >= wo),
              "soft_align_bwd: a leading dimension is smaller than its row");
-  const size_t lds_r = (size_t)tile_lds_floats(tile_plan(lk, mt_max(d, dv))) * sizeof(float);
-  const size_t lds_k = (size_t)key_lds_floats(key_plan(lq, mt_max(d, dv))) * sizeof(float);
+  const size_t lds_r = (size_t)tile_lds_floats(mt_plan(lk, imax(d, dv))) * sizeof(float);
+  const size_t lds_k = (size_t)key_lds_floats(key_plan(lq, imax(d, dv))) * sizeof(float);
   if (int rc = lds_opt_in(sa_bwd_row_kernel, lds_r, "soft_align_bwd")) return rc;
   if (int rc = lds_opt_in(sa_bwd_key_kernel, lds_k, "soft_align_bwd")) return rc;
   hipLaunchKernelGGL(sa_bwd_row_kernel, dim3(b * ((lq + 15) / 16)), dim3(MT_THREADS), lds_r, st, q, k, v, (long long)ldq, (long long)ldk,
@@ -857,7 +694,7 @@ extern "C" int gh_match_dot_fwd(const float* x, const float* y, int ldx, int ldy
   if (int rc = md_check("match_dot_fwd", b, l, r, d)) return rc;
   GH_REQUIRE(x && y && out && (!normalize || (ix && iy)), "match_dot_fwd: NULL argument");
   GH_REQUIRE(ldx >= d && ldy >= d, "match_dot_fwd: a leading dimension is smaller than its row");
-  const size_t lds = (size_t)tile_lds_floats(tile_plan(r, d)) * sizeof(float);
+  const size_t lds = (size_t)tile_lds_floats(mt_plan(r, d)) * sizeof(float);
   if (int rc = lds_opt_in(md_fwd_kernel, lds, "match_dot_fwd")) return rc;
   if (normalize) {
     const long long nx = (long long)b * l, ny = (long long)b * r;
@@ -876,8 +713,8 @@ extern "C" int gh_match_dot_bwd(const float* x, const float* y, int ldx, int ldy
   if (int rc = md_check("match_dot_bwd", b, l, r, d)) return rc;
   GH_REQUIRE(x && y && g && dx && dy && (!normalize || (ix && iy)), "match_dot_bwd: NULL argument");
   GH_REQUIRE(ldx >= d && ldy >= d, "match_dot_bwd: a leading dimension is smaller than its row");
-  const size_t lds_x = (size_t)(tile_lds_floats(tile_plan(r, d))) * sizeof(float);
-  const size_t lds_y = (size_t)(tile_lds_floats(tile_plan(l, d))) * sizeof(float);
+  const size_t lds_x = (size_t)(tile_lds_floats(mt_plan(r, d))) * sizeof(float);
+  const size_t lds_y = (size_t)(tile_lds_floats(mt_plan(l, d))) * sizeof(float);
   if (int rc = lds_opt_in(md_bwd_kernel<false>, lds_x, "match_dot_bwd")) return rc;
   if (int rc = lds_opt_in(md_bwd_kernel<true>, lds_y, "match_dot_bwd")) return rc;
   const float* nx = normalize ? ix : nullptr;

@@ -5,14 +5,9 @@
 // The heads are column slices of the projection GEMMs' outputs, read where they lie ([b][l][heads * d] with a leading
 // dimension), and `out` is written in the layout `fc` consumes: none of the reference's permute copies exists here.
 //
-// All five products run on v_mfma_f32_16x16x4_f32 (exact fp32) from operands staged in LDS.  Two LDS layouts serve them:
-//   KC  element (i, k) at i * pitch + k, pitch % 8 == 4    (the reduction index k is contiguous: Q, K, gO, V as "x^T" operands,
-//       and the 16-row score tile as the left operand of weights v / dS k)
-//   KM  element (k, j) at k * pitch + j, pitch % 32 == 16  (the reduction index is the row: V, K, Q, gO as right operands,
-//       16-key slabs of weights / dS as transposed left operands)
-// With those pitches the 64 lanes of an operand read (lane = 16 * (k & 3) + i) fall into 64 different banks.  Rows are zero-filled
-// to a multiple of 16 and the depth to a multiple of 4 in LDS, so one code path serves every lq, lk, dk and dv; a staging load
-// moves 16 bytes per lane where the source row is 16-byte aligned and whole, and single floats elsewhere.
+// All five products run on the MFMA from operands staged in LDS, in the KC / KM layouts of score_tile.hip.h: Q, K, gO and V
+// are KC as "x^T" operands of the score products and KM as right operands of the second products; the 16-row score tile is the KC
+// left operand of weights v / dS k, and 16-key slabs of weights / dS are the transposed left operands of the key-tiled kernel.
 //
 //   forward            one workgroup per (batch, head, 16-query tile): S = Q K^T into an LDS tile [16][lk] over key chunks,
 //                      row softmax (running maximum subtracted, masked entries exactly 0, a fully masked row all 0), the
@@ -23,6 +18,7 @@
 #include "../../include/get_hip.h"
 #include "common.h"
 #include "device_utils.h"
+#include "score_tile.hip.h"
 #include <math.h>
 
 namespace gh {
@@ -30,6 +26,7 @@ namespace {
 
 constexpr int MHA_THREADS = 256;
 constexpr int MHA_WAVES = MHA_THREADS / 64;
+static_assert(MHA_THREADS == TILE_THREADS, "score_tile.hip.h strides its loops by its own workgroup size");
 constexpr int MHA_MAX_LQ = 1024;
 constexpr int MHA_MAX_LK = 1024;         // one 16-row score tile [16][lk] in LDS (64 KB at the limit)
 constexpr int MHA_MAX_D = 512;           // 32 column tiles of 16: 8 accumulators per wave
@@ -38,15 +35,6 @@ constexpr int MHA_NT = MHA_MAX_D / 16 / MHA_WAVES;      // column tiles per wave
 constexpr int MHA_CHUNK = 9216;          // floats of one staged operand chunk (36 KB): >= 16 rows at the widest pitch (528)
 constexpr int LN_MAX_D = 2048;           // per-wave dgamma / dbeta partials in LDS: 4 x 2 x d floats
 constexpr int LN_MAX_WG = 256;
-
-__host__ __device__ inline int pitch_km(int n) { n = up16(n); return (n & 31) == 16 ? n : n + 16; }
-// rows of a chunk with `pitch` floats per row: a multiple of 16, at least 16, at most the padded extent
-__host__ __device__ inline int chunk_rows(int extent, int pitch, int budget) {
-  int r = (budget / pitch) & ~15;
-  if (r < 16) r = 16;
-  const int e = up16(extent);
-  return r < e ? r : e;
-}
 
 struct FwdPlan { int pq, ps, pk, pv, kc1, kc2, chunk; };      // pitches, key-chunk rows of the two products, chunk floats
 __host__ __device__ inline FwdPlan fwd_plan(int lk, int da, int db) {
@@ -74,10 +62,13 @@ __host__ __device__ inline KeyPlan key_plan(int lq, int dk, int dv) {
 }
 __host__ __device__ inline int key_lds_floats(const KeyPlan& p) { return p.qc * (p.pqm + p.pgm + 32); }
 
+// This file's own forms of score_tile.hip.h's `stage` and `mma_scores`, kept because the shared forms change these kernels'
+// device code and that change was not measured: the tail tests here compare c + i with cols where ld4 compares
+// cols - c with i, and the score store below indexes ss where the shared one, which also reloads, walks a hoisted pointer.
 // rows x cols of a row-major source -> LDS [rows_pad][pitch], zero-filled beyond (rows, cols); cols_pad % 4 == 0
-__device__ __forceinline__ void stage(float* dst, int pitch, int rows_pad, int cols_pad, const float* __restrict__ src, long long ld,
-                                      int rows, int cols) {
-  const bool vec = (reinterpret_cast<uintptr_t>(src) & 15) == 0 && (ld & 3) == 0;
+__device__ __forceinline__ void mha_stage(float* dst, int pitch, int rows_pad, int cols_pad, const float* __restrict__ src, long long ld,
+                                          int rows, int cols) {
+  const bool vec = vec_ok(src, ld);
   const int c4n = cols_pad >> 2;
   for (int idx = threadIdx.x; idx < rows_pad * c4n; idx += MHA_THREADS) {
     const int r = idx / c4n, c = (idx - r * c4n) << 2;
@@ -97,26 +88,8 @@ __device__ __forceinline__ void stage(float* dst, int pitch, int rows_pad, int c
   }
 }
 
-// LDS tile [16][pitch] (only the first `rows` rows and `cols` columns) -> row-major global, 16 bytes per lane where possible
-__device__ __forceinline__ void unstage(float* __restrict__ dst, long long ld, const float* src, int pitch, int rows, int cols) {
-  const bool vec = (reinterpret_cast<uintptr_t>(dst) & 15) == 0 && (ld & 3) == 0 && (cols & 3) == 0;
-  if (vec) {
-    const int c4n = cols >> 2;
-    for (int idx = threadIdx.x; idx < rows * c4n; idx += MHA_THREADS) {
-      const int r = idx / c4n, c = (idx - r * c4n) << 2;
-      *reinterpret_cast<float4*>(dst + (size_t)r * ld + c) = *reinterpret_cast<const float4*>(src + r * pitch + c);
-    }
-  } else {
-    for (int idx = threadIdx.x; idx < rows * cols; idx += MHA_THREADS) {
-      const int r = idx / cols, c = idx - r * cols;
-      dst[(size_t)r * ld + c] = src[r * pitch + c];
-    }
-  }
-}
-
-// S[16][key0 + ...] = X Y^T for a chunk: X = xs [16][px] (KC), Y = ys [rows_pad][py] (KC), depth % 4 == 0.  Wave w owns the
-// 16-column tiles w, w + 4, ...; C/D map: column = lane & 15, row = 4 (lane >> 4) + r.
-__device__ __forceinline__ void mma_scores(const float* xs, int px, const float* ys, int py, int rows_pad, int depth, float* ss, int ps,
+// S[16][key0 + ...] = X Y^T for a chunk: X = xs [16][px] (KC), Y = ys [rows_pad][py] (KC), depth % 4 == 0; the whole depth in one call
+__device__ __forceinline__ void mha_scores(const float* xs, int px, const float* ys, int py, int rows_pad, int depth, float* ss, int ps,
                                            int key0) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, qd = lane >> 4;
   for (int jt = wave; jt < (rows_pad >> 4); jt += MHA_WAVES) {
@@ -132,20 +105,6 @@ __device__ __forceinline__ void mma_scores(const float* xs, int px, const float*
     acc0 += acc1;
 #pragma unroll
     for (int r = 0; r < 4; ++r) ss[(4 * qd + r) * ps + key0 + jt * 16 + l15] = acc0[r];
-  }
-}
-
-// acc[t] += A B for the column tiles ct = wave + 4 t < ntiles: A element (i, k) at as[i * sai + k * sak], B = bs [kk][pb] (KM)
-__device__ __forceinline__ void mma_acc(const float* as, int sai, int sak, const float* bs, int pb, int kk, int ntiles, f32x4* acc) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, qd = lane >> 4;
-  const float* ap = as + l15 * sai + qd * sak;
-  const float* bp = bs + qd * pb + wave * 16 + l15;
-  for (int k0 = 0; k0 < kk; k0 += 4) {
-    const float a = ap[k0 * sak];
-#pragma unroll
-    for (int t = 0; t < MHA_NT; ++t)
-      if (wave + MHA_WAVES * t < ntiles)
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp[k0 * pb + t * 16 * MHA_WAVES], acc[t], 0, 0, 0);
   }
 }
 
@@ -179,13 +138,13 @@ mha_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const f
   const int nq = min(16, lq - q0);
   const int dk4 = up4(dk);
 
-  stage(qs, P.pq, 16, dk4, q + ((size_t)bi * lq + q0) * ldq + (size_t)h * dk, ldq, nq, dk);
+  mha_stage(qs, P.pq, 16, dk4, q + ((size_t)bi * lq + q0) * ldq + (size_t)h * dk, ldq, nq, dk);
   for (int key0 = 0; key0 < lk; key0 += P.kc1) {
     const int nk = min(P.kc1, lk - key0), rp = up16(nk);
     __syncthreads();
-    stage(ch, P.pk, rp, dk4, k + ((size_t)bi * lk + key0) * ldk + (size_t)h * dk, ldk, nk, dk);
+    mha_stage(ch, P.pk, rp, dk4, k + ((size_t)bi * lk + key0) * ldk + (size_t)h * dk, ldk, nk, dk);
     __syncthreads();
-    mma_scores(qs, P.pq, ch, P.pk, rp, dk4, ss, P.ps, key0);
+    mha_scores(qs, P.pq, ch, P.pk, rp, dk4, ss, P.ps, key0);
   }
   __syncthreads();
   {      // softmax: 16 lanes per row
@@ -220,9 +179,9 @@ mha_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const f
   for (int key0 = 0; key0 < lk; key0 += P.kc2) {
     const int nk = min(P.kc2, lk - key0), rp = up4(nk);
     __syncthreads();
-    stage(ch, P.pv, rp, up16(dv), v + ((size_t)bi * lk + key0) * ldv + (size_t)h * dv, ldv, nk, dv);
+    mha_stage(ch, P.pv, rp, up16(dv), v + ((size_t)bi * lk + key0) * ldv + (size_t)h * dv, ldv, nk, dv);
     __syncthreads();
-    mma_acc(ss + key0, P.ps, 1, ch, P.pv, rp, nct, acc);
+    mma_acc<MHA_NT>(ss + key0, P.ps, 1, ch, P.pv, rp, nct, acc);
   }
   store_acc(out + ((size_t)bi * lq + q0) * ldo + (size_t)h * dv, ldo, nq, dv, acc);
 }
@@ -244,13 +203,13 @@ mha_bwd_q_kernel(const float* __restrict__ k, const float* __restrict__ v, long 
   const int dv4 = up4(dv);
   const size_t wbase = (((size_t)h * b + bi) * lq + q0) * lk;
 
-  stage(gs, P.pq, 16, dv4, g_out + ((size_t)bi * lq + q0) * ldgo + (size_t)h * dv, ldgo, nq, dv);
+  mha_stage(gs, P.pq, 16, dv4, g_out + ((size_t)bi * lq + q0) * ldgo + (size_t)h * dv, ldgo, nq, dv);
   for (int key0 = 0; key0 < lk; key0 += P.kc1) {      // dA = gO V^T
     const int nk = min(P.kc1, lk - key0), rp = up16(nk);
     __syncthreads();
-    stage(ch, P.pk, rp, dv4, v + ((size_t)bi * lk + key0) * ldv + (size_t)h * dv, ldv, nk, dv);
+    mha_stage(ch, P.pk, rp, dv4, v + ((size_t)bi * lk + key0) * ldv + (size_t)h * dv, ldv, nk, dv);
     __syncthreads();
-    mma_scores(gs, P.pq, ch, P.pk, rp, dv4, ss, P.ps, key0);
+    mha_scores(gs, P.pq, ch, P.pk, rp, dv4, ss, P.ps, key0);
   }
   __syncthreads();
   {      // dS = A (dA - rowsum(A dA)), dA = g_w + gO V^T; exact zeros where the weight is 0
@@ -288,9 +247,9 @@ mha_bwd_q_kernel(const float* __restrict__ k, const float* __restrict__ v, long 
   for (int key0 = 0; key0 < lk; key0 += P.kc2) {      // dq = dS K
     const int nk = min(P.kc2, lk - key0), rp = up4(nk);
     __syncthreads();
-    stage(ch, P.pv, rp, up16(dk), k + ((size_t)bi * lk + key0) * ldk + (size_t)h * dk, ldk, nk, dk);
+    mha_stage(ch, P.pv, rp, up16(dk), k + ((size_t)bi * lk + key0) * ldk + (size_t)h * dk, ldk, nk, dk);
     __syncthreads();
-    mma_acc(ss + key0, P.ps, 1, ch, P.pv, rp, nct, acc);
+    mma_acc<MHA_NT>(ss + key0, P.ps, 1, ch, P.pv, rp, nct, acc);
   }
   store_acc(dq + ((size_t)bi * lq + q0) * lddq + (size_t)h * dk, lddq, nq, dk, acc);
 }
@@ -319,13 +278,13 @@ mha_bwd_k_kernel(const float* __restrict__ q, long long ldq, const float* __rest
   for (int r0 = 0; r0 < lq; r0 += P.qc) {
     const int nr = min(P.qc, lq - r0), rp = up4(nr);
     __syncthreads();
-    stage(qc, P.pqm, rp, up16(dk), q + ((size_t)bi * lq + r0) * ldq + (size_t)h * dk, ldq, nr, dk);
-    stage(gc, P.pgm, rp, up16(dv), g_out + ((size_t)bi * lq + r0) * ldgo + (size_t)h * dv, ldgo, nr, dv);
-    stage(dst, 16, rp, 16, ds + wbase + (size_t)r0 * lk, lk, nr, nk);
-    stage(wt, 16, rp, 16, weights + wbase + (size_t)r0 * lk, lk, nr, nk);
+    mha_stage(qc, P.pqm, rp, up16(dk), q + ((size_t)bi * lq + r0) * ldq + (size_t)h * dk, ldq, nr, dk);
+    mha_stage(gc, P.pgm, rp, up16(dv), g_out + ((size_t)bi * lq + r0) * ldgo + (size_t)h * dv, ldgo, nr, dv);
+    mha_stage(dst, 16, rp, 16, ds + wbase + (size_t)r0 * lk, lk, nr, nk);
+    mha_stage(wt, 16, rp, 16, weights + wbase + (size_t)r0 * lk, lk, nr, nk);
     __syncthreads();
-    mma_acc(dst, 1, 16, qc, P.pqm, rp, nctk, acck);      // dk = dS^T Q
-    mma_acc(wt, 1, 16, gc, P.pgm, rp, nctv, accv);       // dv = A^T gO
+    mma_acc<MHA_NT>(dst, 1, 16, qc, P.pqm, rp, nctk, acck);      // dk = dS^T Q
+    mma_acc<MHA_NT>(wt, 1, 16, gc, P.pgm, rp, nctv, accv);       // dv = A^T gO
   }
   store_acc(dkk + ((size_t)bi * lk + key0) * lddk + (size_t)h * dk, lddk, nk, dk, acck);
   store_acc(dvv + ((size_t)bi * lk + key0) * lddv + (size_t)h * dv, lddv, nk, dv, accv);

@@ -167,3 +167,22 @@ def test_stateless_dropout_mask_is_unbiased_and_uncorrelated():
         assert abs(float((c * k2).mean()) / (p * q)) <= 4.0 / np.sqrt(n)
         k3 = dropout_mask_reference(seed ^ 0x5bd1e995, rows, cols, p).astype(np.float64) - q
         assert abs(float((c * k3).mean()) / (p * q)) <= 4.0 / np.sqrt(n)
+
+
+def test_makefile_hdr_lists_every_quoted_include():
+    """csrc/Makefile rebuilds an object when a file of HDR changes, so a header missing from HDR leaves stale objects behind:
+    every file that a csrc/*.hip or csrc/*.h includes with quotes from csrc/ or include/ is listed there."""
+    import pathlib
+    import re
+    root = pathlib.Path(__file__).resolve().parent.parent
+    csrc = root / "get_amd" / "csrc"
+    make = (csrc / "Makefile").read_text().replace("\\\n", " ")
+    hdr = {(csrc / h).resolve() for h in re.search(r"^HDR\s*:=(.*)$", make, re.M).group(1).split()}
+    assert hdr and all(h.is_file() for h in hdr)
+    sources = sorted(list(csrc.glob("*.hip")) + list(csrc.glob("*.h")))
+    assert sources
+    for src in sources:
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', src.read_text(), re.M):
+            path = (src.parent / inc).resolve()
+            if path.parent in (csrc, root / "include"):
+                assert path in hdr, f"{src.name} includes {inc}, which HDR of csrc/Makefile does not list"
