@@ -128,7 +128,7 @@ int launch_att_dpre(const float* de, const float* w2, const float* t, const int3
 // epilogue (EPI_GATE_PRE): the cell's saved z / hh / xp and its dhp / dzp / dxp scratch (all [rows][h] fp32).
 struct GateFuse { const float* z; const float* hh; const float* xp; float* dhp; float* dzp; float* dxp; int bf16; };      // bf16: all six hold bf16 (bf16 storage pipeline)
 
-// fused building blocks shared by the per-module entry points (gemm_ops.hip) and the composite model entry points
+// fused building blocks shared by the per-module entry points (cell_ops.hip, dense_ops.hip) and the composite model entry points
 // (model_ops.hip); argument meaning as the gh_* functions of the same name in include/get_hip.h
 int cell_fwd_impl(int bf, float* out32, const uint64_t* bits, const float* dinv, const float* vals, const uint64_t* keep,
                   const int32_t* goff, int m_real, int m_rows, const float* x, const int32_t* ids, int n, int r, int din, int h,

@@ -1,5 +1,5 @@
 // Composite entry points: the whole GET forward / backward as ONE library call each (include/get_hip.h "a7"), the fused
-// cross-entropy and the one-call batch preparation.  Host-side chaining of the fused building blocks of gemm_ops.hip /
+// cross-entropy and the one-call batch preparation.  Host-side chaining of the fused building blocks of cell_ops.hip / dense_ops.hip /
 // graph_ops.hip / misc_ops.hip on two streams, plus the few small kernels that replace the at::native glue the
 // module-by-module path needed (lens casts, `* has`, torch.cat, index_copy_, the CE kernels).
 //
@@ -80,7 +80,7 @@ static int make_dims(const gh_get_model* Mo, const gh_get_batch* Ba, Dims& d) {
     GH_REQUIRE(Mo->embedding16, "get: storage = 1 needs the bf16 copy of the word table (embedding16)");
   }
   // att16 = "no fp32 copy of the second cell's output exists": it must imply every condition of att_fwd_impl's / att_bwd_impl's own
-  // use16 predicate (gemm_ops.hip: bf16 gemm mode, >= 8192 rows, right / left / hidden widths multiples of 8) -- restated here in
+  // use16 predicate (dense_ops.hip: bf16 gemm mode, >= 8192 rows, right / left / hidden widths multiples of 8) -- restated here in
   // full rather than relied upon by construction (d.bf already holds Mr >= 8192 and H % 8 == 0; the word attention's right and
   // left widths and its hidden width are all H)
   d.att16 = d.bf && gemm_mode() == 1 && Mo->att_word_w1_16 && Mo->att_word_w1t_16 && d.Mr >= 8192 && d.H % 8 == 0;

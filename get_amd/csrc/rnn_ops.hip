@@ -5,7 +5,7 @@
 //   gh_gru_seq_fwd    h_t over t from gx = x W_ih^T + b_ih, W_hh and b_hh (b_hn sits inside the product with r: it cannot be folded)
 //   gh_gru_seq_bwd    the gradients of gx and of the recurrent pre-activations over t, walking time the other way
 // Only the sequential part lives here: the input projection, its gradients and dW_hh = dgates^T h_prev are activation-sized GEMMs
-// of gemm_ops.hip.  Both directions of a layer run in one launch (grid y).
+// of gh_linear_* (dense_ops.hip).  Both directions of a layer run in one launch (grid y).
 //
 // One workgroup of 8 waves owns a tile of 16 sequences (the M of v_mfma_f32_16x16x4_f32, exact fp32) and all 4h gate columns of
 // its direction.  Tiles are independent: no workgroup waits for another, every loop's trip count comes from the clamped lengths.

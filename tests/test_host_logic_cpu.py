@@ -186,3 +186,31 @@ def test_makefile_hdr_lists_every_quoted_include():
             path = (src.parent / inc).resolve()
             if path.parent in (csrc, root / "include"):
                 assert path in hdr, f"{src.name} includes {inc}, which HDR of csrc/Makefile does not list"
+
+
+def test_makefile_src_lists_every_hip_file():
+    """csrc/Makefile links the objects of SRC: a csrc/*.hip that is missing there only shows up as an undefined symbol when the
+    library is loaded."""
+    import pathlib
+    import re
+    csrc = pathlib.Path(__file__).resolve().parent.parent / "get_amd" / "csrc"
+    make = (csrc / "Makefile").read_text().replace("\\\n", " ")
+    src = re.search(r"^SRC\s*:=(.*)$", make, re.M).group(1).split()
+    assert len(src) == len(set(src))
+    assert sorted(src) == sorted(p.name for p in csrc.glob("*.hip"))
+
+
+def test_layer_files_hold_no_kernel():
+    """The layers on the GEMM engine (every csrc/*.hip that includes gemm_batch.h, except the engine gemm_ops.hip itself) are host
+    code that compiles in seconds: no kernel, no kernel launch, none of the NT / TN kernel headers."""
+    import pathlib
+    import re
+    csrc = pathlib.Path(__file__).resolve().parent.parent / "get_amd" / "csrc"
+    layers = {p.name: p.read_text() for p in csrc.glob("*.hip")
+              if p.name != "gemm_ops.hip" and re.search(r'^\s*#\s*include\s+"gemm_batch\.h"', p.read_text(), re.M)}
+    assert {"cell_ops.hip", "dense_ops.hip"} <= set(layers)
+    for name, text in layers.items():
+        assert "__global__" not in text, name
+        assert "hipLaunchKernelGGL" not in text and "<<<" not in text, name
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', text, re.M):
+            assert not re.match(r"gemm_(nt|tn).*\.hip\.h$", pathlib.PurePath(inc).name), f"{name} includes {inc}"
