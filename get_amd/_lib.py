@@ -105,6 +105,7 @@ SIGNATURES = {
     "gh_cross_entropy": [_P, _P, _I, _I, _P, _P, _P],
     "gh_get_prepare": [_P, _P, _I, _I, _P, _P, _I, _I, _I] + [_P] * 8 + [_I] + [_P] * 5 + [_P, _P, _P],
     "gh_get_struct_sizes": [_P],
+    "gh_cls_metrics": [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P],
     # library-owned RCCL communicator (csrc/comm_ops.hip; librccl is dlopen'ed on first use)
     "gh_comm_unique_id": [_P],
     "gh_comm_init": [_P, _I, _I, _P],

@@ -24,6 +24,25 @@ class KeyWordSettings(object):
     TempLabel = "fc_labels"
     UseCuda = "use_cuda"
 
+    # keys of the results dict of the fitter's evaluate (char_man_fitter_query_repr1.py:403-418), get_amd.evaluate's as well
+    AUC_metric = "auc"
+    F1_macro = "f1_macro"
+    F1_micro = "f1_micro"
+    F1 = "f1"
+    PrecisionTrueCls = "precision_true_cls"
+    RecallTrueCls = "recall_true_cls"
+    F1TrueCls = "f1_true_cls"
+    PrecisionFalseCls = "precision_false_cls"
+    RecallFalseCls = "recall_false_cls"
+    F1FalseCls = "f1_false_cls"
+    PrecisionMixedCls = "precision_mixed_cls"
+    RecallMixedCls = "recall_mixed_cls"
+    F1MixedCls = "f1_mixed_cls"
+    CLS_METRICS = [AUC_metric, F1_macro, F1_micro, F1,
+                   PrecisionTrueCls, RecallTrueCls, F1TrueCls,
+                   PrecisionFalseCls, RecallFalseCls, F1FalseCls,
+                   PrecisionMixedCls, RecallMixedCls, F1MixedCls]
+
     class FCClass:
         CharSourceKey = "char_source"
         QueryCharSource = "query_char_source"

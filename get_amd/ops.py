@@ -1829,6 +1829,35 @@ def backward(loss):
     _bw(loss)
 
 
+# --------------------------------------------------------------------------- evaluation
+CLS_EXTRA = 8            # slots of gh_cls_metrics' `out` behind the c x c confusion matrix
+
+
+def cls_metrics(phi, labels, pos_class: int = 1):
+    """The integers of the fitter's metrics (char_man_fitter_query_repr1.py:353-362, 381-401) in one launch, no read-back.
+
+    phi (n, c) float32 logits -- rows may be a column slice of a wider row-major tensor (unit column stride) --, labels (n,)
+    int64 or int32.  Returns (out (c*c + 8,) int64, pred (n,) int32) on the device; include/get_hip.h (gh_cls_metrics) lists
+    the slots of `out`: confusion counts [label][prediction], then U2, n_pos, n_neg, bad labels, NaN rows."""
+    _lib.require_cuda(phi, labels)
+    if phi.dim() != 2 or labels.dim() != 1 or labels.shape[0] != phi.shape[0]:
+        raise ValueError(f"cls_metrics: phi (n, c) and labels (n,) expected, got {tuple(phi.shape)} and {tuple(labels.shape)}")
+    phi = phi.detach()
+    n, c = phi.shape
+    if phi.dtype != torch.float32 or phi.stride(1) != 1 or phi.stride(0) < c or phi.data_ptr() % 4:
+        phi = phi.float().contiguous()
+    if labels.dtype not in (torch.int64, torch.int32):
+        labels = labels.to(torch.int64)
+    labels = labels.contiguous()
+    if phi.device != labels.device or phi.device.index != _lib._get_device():
+        raise RuntimeError("get_amd: cls_metrics wants phi and labels on the current device")
+    out = torch.empty((c * c + CLS_EXTRA,), device=phi.device, dtype=torch.int64)
+    pred = torch.empty((n,), device=phi.device, dtype=torch.int32)
+    call("gh_cls_metrics", phi.data_ptr(), phi.stride(0) if n > 1 else c, ptr(labels), 1 if labels.dtype == torch.int64 else 0,
+         n, c, int(pos_class), ptr(pred), ptr(out), stream())
+    return out, pred
+
+
 # --------------------------------------------------------------------------- optimiser
 def adam_step_flat(p, g, m, v, step, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-3, grad_scale=1.0):
     """One Adam step on flat fp32 buffers (declare_fitter.py:58-61 semantics)."""

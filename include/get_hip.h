@@ -748,6 +748,28 @@ int gh_get_prepare(const int32_t* claim_tokens, const int32_t* claim_len, int b,
                    int m_real, int32_t* goff, int32_t* rowg, int32_t* src, int32_t* cids, float* maskf,
                    const int64_t* slot, int32_t* document, gh_stream_t stream);
 
+/* ---- evaluation: the integers the fitter's metrics are exact functions of (Fitting/FittingFC/char_man_fitter_query_repr1.py:353
+ *      and :358 `probs.argmax(dim=1)`, :360 `probs[:, 1]`, :362 and :381-401 `_computing_metrics`' sklearn calls) from logits
+ *      phi [n] rows of c floats, ldphi >= c floats apart, and labels [n] (int64 when labels_i64, else int32).  No softmax is applied:
+ *      the reference ranks by the raw logit.
+ *   pred [n] (NULL ok): argmax of every row, the first index among equal maxima (a NaN counts as the maximum, as in torch.argmax).
+ *   out [c*c + 8], written as a whole:
+ *     out[t*c + p]  rows with label t and prediction p
+ *     out[c*c + 0]  U2 = sum over rows i with label == pos_class and rows j with label != pos_class of
+ *                   2 [s_i > s_j] + [s_i == s_j], s = phi[:, pos_class], IEEE comparison (-0.0 == 0.0, +-inf ordinary values):
+ *                   AUC = U2 / (2 n_pos n_neg), the trapezoid area of roc_curve(pos_label = pos_class) + auc
+ *     out[c*c + 1]  n_pos, rows with label == pos_class;  out[c*c + 2]  n_neg, rows with any other label in [0, c)
+ *     out[c*c + 3]  rows whose label lies outside [0, c): left out of every other count
+ *     out[c*c + 4]  rows (with a label in [0, c)) that hold a NaN among their c logits: left out of every other count
+ *     out[c*c + 5 .. 7]  reserved, zero
+ * Integer arithmetic throughout (64-bit integer atomic adds of per-workgroup sums into `out`, no floating-point atomics): the
+ * result is exact and independent of tiling and launch geometry.  Limits: 2 <= c <= GH_CLS_MAX_CLASSES,
+ * 1 <= n <= GH_CLS_MAX_ROWS (the launch grid and the 32-bit row index; n = 0 is rejected), 0 <= pos_class < c. */
+#define GH_CLS_MAX_CLASSES 8
+#define GH_CLS_MAX_ROWS (1 << 20)
+int gh_cls_metrics(const float* phi, int ldphi, const void* labels, int labels_i64, int n, int c, int pos_class,
+                   int32_t* pred, int64_t* out, gh_stream_t stream);
+
 /* Everything the forward / backward need that is DERIVED from weight matrices, for n matrices in one launch (after the
  * optimiser step): dst_t[i] = src[i]^T as fp32 [cols][rows] (the backward's dX operands), and -- bf16 storage mode, any of the
  * two arrays or any entry may be NULL -- dst_w16[i] = bf16(src[i]) [rows][cols], dst_t16[i] = bf16(src[i]^T) [cols][rows]. */
