@@ -30,7 +30,7 @@ int gh::cell_fwd_impl(int bf, float* out32, const uint64_t* bits, const float* d
   const int M = m_rows;
   if (M == 0) return 0;
   GH_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "ggnn_cell_fwd: dropout p=%f not in [0,1)", drop_p);
-  // the stateless dropout mask hashes a 32-BIT element index row * width + column (gemm.hip.h drop_hash): beyond 2^32 elements
+  // the stateless dropout mask hashes a 32-BIT element index row * width + column (device_utils.h drop_hash): beyond 2^32 elements
   // two rows would share their mask
   GH_REQUIRE((drop_p <= 0.f && score_drop_p <= 0.f) || (long long)M * (long long)(din > h ? din : h) < (1LL << 32),
              "ggnn_cell_fwd: %d rows x %d columns exceed the dropout mask's 32-bit element index", M, din > h ? din : h);

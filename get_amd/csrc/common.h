@@ -1,4 +1,5 @@
-// Shared host-side helpers of libget_hip.so (error reporting, internal launch prototypes).
+// Shared host-side helpers of libget_hip.so: error reporting and the event profiler (runtime_ops.hip), and the prototypes of the
+// internal launchers, grouped by the file that implements them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -64,11 +65,15 @@ enum ProfTag : int {
 };
 // streaming-kernel launches over fewer than this many graphs / pairs are booked under PROF_FEW_ROWS
 constexpr int PROF_FEW_GROUPS = 256;
-unsigned int* clamp_counter();      // four device counters of clamped out-of-range inputs on the current device (gh_clamp_events); NULL = allocation failed
+inline int few_rows_tag(int groups, int tag) { return groups < PROF_FEW_GROUPS ? PROF_FEW_ROWS : tag; }
 bool prof_enabled();
 void prof_begin(hipStream_t s, int tag);   // events are recorded only for tags selected by gh_profile_select
 void prof_end(int tag, double work, hipStream_t s);
+unsigned int* clamp_counter();      // four device counters of clamped out-of-range inputs on the current device (gh_clamp_events); NULL = allocation failed
 
+// Internal launchers used by the fused entry points, one group per implementing file.
+
+// ---- graph_ops.hip
 // gh_scorer_gsl with the projection arriving as score_parts partial tensors, score_stride floats apart (wide cell outputs)
 int scorer_gsl_impl(const uint64_t* bits, const float* dinv, const float* vals, const int32_t* goff, int pads_collapsed, const float* feat,
                     const float* score_x, int score_parts, long long score_stride, const float* w_p, const float* gate, int n, int r, int h,
@@ -79,51 +84,57 @@ int launch_graph_build2(const int32_t* ta, const int32_t* la, int na, int ra, in
                         const int32_t* tb, const int32_t* lb, int nb, int rb, int32_t* idb, int32_t* nnb, uint64_t* bb, float* db,
                         int window, hipStream_t s);
 struct ZeroFill { float* p0; long long n0; float* p1; long long n1; };      // n in floats, multiples of 4, 16-byte aligned pointers
-// internal launchers implemented in graph_ops.hip / misc_ops.hip, used by the fused entry points
 // goff != NULL: node-compact layout (include/get_hip.h) -- graph g owns rows [goff[g], goff[g+1]); m_real = goff[n]
+// zf: up to two float ranges the launch zero-fills on its way (the cell forward's padding rows of `a` and the scorer's partial
+// dot products: two memset dispatches per step otherwise); *zf_done says whether the kernel variant that ran supports it
 int launch_spmm(const uint64_t* bits, const float* dinv, const float* vals, const uint64_t* keep, const int32_t* goff,
                 int m_real, const float* x, float* y, int n, int r, int h, int transpose, int accumulate, hipStream_t s,
                 int bf16 = 0,       // bf16: x and y hold bf16
                 const ZeroFill* zf = nullptr, bool* zf_done = nullptr);
-// zf: up to two float ranges the launch zero-fills on its way (the cell forward's padding rows of `a` and the scorer's partial
-// dot products: two memset dispatches per step otherwise); *zf_done says whether the kernel variant that ran supports it
+
+// ---- stream_ops.hip
 int launch_gate_bwd_pre(const float* g, const float* z, const float* hh, const float* xp, float* dhp, float* dzp,
                         float* dxp, size_t count, hipStream_t s, int bf16 = 0);   // bf16: everything but g holds bf16
 int launch_colsum3(const float* a, const float* b, const float* c, float* oa, float* ob, float* oc, int m, int h,
                    hipStream_t s, float* oa2 = nullptr, float* ob2 = nullptr, float* oc2 = nullptr);
 int launch_colsum(const float* a, float* oa, int m, int h, hipStream_t s);
-// Scratch registered by the caller: per stream (gh_set_stream_workspace) or the process default (gh_set_workspace).
-// `p` serves the split-K partial tiles, `cs` (the last 1/16) the column-sum partials.
-struct Workspace { float* p; size_t bytes; float* cs; size_t cs_bytes; };
-Workspace workspace_for(hipStream_t s);
 int launch_gather_rows(const float* table, const int32_t* ids, float* dst, int m, int d, hipStream_t s,
                        float drop_p = 0.f, unsigned drop_seed = 0, int bf16 = 0);   // bf16: table and dst hold bf16
 int launch_tiny_linear_fwd(const float* x, const float* w, const float* bias, float* y, int m, int k, int n, hipStream_t s);
-// head backward in one launch (misc_ops.hip head_bwd_kernel): d_y0 = g_phi w1; [dx0 | dx1] = d_y0 w0 (w0 as stored, [H][E]); dw1 / db1 +=
+int launch_tiny_linear_bwd(const float* x, const float* w, const float* g, float* dx, float* dw, float* db, int m, int k, int n,
+                           hipStream_t s);
+// head backward in one launch (head_bwd_kernel): d_y0 = g_phi w1; [dx0 | dx1] = d_y0 w0 (w0 as stored, [H][E]); dw1 / db1 +=
 int launch_head_bwd(const float* g_phi, const float* y0, const float* w1, const float* w0, int B, int H, int C, int Xl, int E,
                     float* d_y0, float* dw1, float* db1, float* dx0, int dx0_accumulate, float* dx1, hipStream_t s);
 size_t head_bwd_lds(int B, int H, int C, int E, const float* w0);      // 0: the sizes do not fit its LDS staging
-int launch_tiny_linear_bwd(const float* x, const float* w, const float* g, float* dx, float* dw, float* db, int m, int k, int n,
-                           hipStream_t s);
+
+// ---- concat_att_ops.hip
+// (e_parts: n_parts partial score tensors [rows][heads], part_stride floats apart -- one per column block of a wide hidden
+//  layer; the kernel sums them in block order and writes the sum to e)
+// (right16: the right operand as bf16 rows -- bf16 storage mode; `right` may then be NULL on the row-balanced / forward kernels)
 int launch_att_softmax_fwd(float* e, const float* mask, const float* right, const int32_t* goff, int m_real,
                            int b, int l, int dr, int heads, float* weights, float* attended, hipStream_t s,
                            const float* e_parts = nullptr, int n_parts = 0, long long part_stride = 0, const void* right16 = nullptr);
-// (e_parts: n_parts partial score tensors [rows][heads], part_stride floats apart -- one per column block of a wide hidden
-//  layer; the kernel sums them in block order and writes the sum to e)
+// (rowg + dw_tmp [ceil(dr / 512)][rows][heads] + dw_written: many-pair launches may take the row-balanced kernel, which leaves the raw
+//  dw in dw_tmp instead of de -- *dw_written = the number of column ranges (<= 16) rows wider than 512 floats were split into, whose
+//  partial dw sit rows * heads floats apart -- and launch_att_dpre(dw_in = dw_tmp, weights, de_out = de, .., stride, ranges) finishes de)
 int launch_att_softmax_bwd(const float* right, const float* weights, const float* g_att, const float* g_w,
                            const int32_t* goff, int m_real, int b, int l, int dr, int heads, float* de, float* dright,
                            hipStream_t s, const int32_t* rowg = nullptr, float* dw_tmp = nullptr, int* dw_written = nullptr,
                            const void* right16 = nullptr);
-// (right16: the right operand as bf16 rows -- bf16 storage mode; `right` may then be NULL on the row-balanced / forward kernels)
-int gemm_mode();      // gh_set_gemm_mode's current value
-// (rowg + dw_tmp [ceil(dr / 512)][rows][heads] + dw_written: many-pair launches may take the row-balanced kernel, which leaves the raw
-//  dw in dw_tmp instead of de -- *dw_written = the number of column ranges (<= 16) rows wider than 512 floats were split into, whose
-//  partial dw sit rows * heads floats apart -- and launch_att_dpre(dw_in = dw_tmp, weights, de_out = de, .., stride, ranges) finishes de)
 int launch_att_dpre(const float* de, const float* w2, const float* t, const int32_t* goff, int m_real, int b, int l,
                     int ha, int heads, float* dpre, float* du, float* dw2_part, hipStream_t s, const float* dw_in = nullptr,
                     const float* weights = nullptr, float* de_out = nullptr, void* dpre16 = nullptr,       // dpre16: dpre as bf16 there instead
                     long long dw_range_stride = 0, int dw_ranges = 1);      // dw_ranges > 1: dw_in = that many column-range partials of att_rows_bwd (rows wider than 512 floats)
 
+// ---- gemm_ops.hip
+// Scratch registered by the caller: per stream (gh_set_stream_workspace) or the process default (gh_set_workspace).
+// `p` serves the split-K partial tiles, `cs` (the last 1/16) the column-sum partials.
+struct Workspace { float* p; size_t bytes; float* cs; size_t cs_bytes; };
+Workspace workspace_for(hipStream_t s);
+int gemm_mode();      // gh_set_gemm_mode's current value
+
+// ---- cell_ops.hip / dense_ops.hip
 // Where the gradient w.r.t. a GGNN cell's output goes when the GEMM that produces it applies that cell's gate head in its
 // epilogue (EPI_GATE_PRE): the cell's saved z / hh / xp and its dhp / dzp / dxp scratch (all [rows][h] fp32).
 struct GateFuse { const float* z; const float* hh; const float* xp; float* dhp; float* dzp; float* dxp; int bf16; };      // bf16: all six hold bf16 (bf16 storage pipeline)

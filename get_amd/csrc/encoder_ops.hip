@@ -5,7 +5,6 @@
 #include "../../include/get_hip.h"
 #include "common.h"
 #include "device_utils.h"
-#include "gemm.hip.h"
 #include <math.h>
 
 namespace gh {

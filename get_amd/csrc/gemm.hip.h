@@ -19,10 +19,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
+#include "device_utils.h"      // f32x4, drop_hash / drop4, sigmoidf_ / tanhf_, pack_bf2 (the fast paths)
 
 namespace gh {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 enum EpiKind : int {
   EPI_STORE = 0,   // C = v (+bias[col]) (+C when accumulate)
@@ -95,26 +94,6 @@ static_assert(sizeof(Launch) <= 4096, "Launch travels by value in the kernarg se
 constexpr int DBG_NO_EPILOGUE = 1;      // K loop only
 constexpr int DBG_NO_KLOOP = 2;         // epilogue only (one K tile)
 constexpr int DBG_EPI_TICKS = 1024;     // 256-tile epilogue: per-kind tick sums into g_nt_phase (gh_debug_nt_phases)
-
-__host__ __device__ __forceinline__ unsigned drop_hash(unsigned seed, unsigned idx) {
-  unsigned x = idx * 0x9E3779B1u + seed;
-  x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
-  return x;
-}
-__device__ __forceinline__ float4 drop4(float4 v, unsigned seed, unsigned idx, unsigned thresh, float scale) {
-  v.x = drop_hash(seed, idx + 0) >= thresh ? v.x * scale : 0.f;
-  v.y = drop_hash(seed, idx + 1) >= thresh ? v.y * scale : 0.f;
-  v.z = drop_hash(seed, idx + 2) >= thresh ? v.z * scale : 0.f;
-  v.w = drop_hash(seed, idx + 3) >= thresh ? v.w * scale : 0.f;
-  return v;
-}
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
-__device__ __forceinline__ float tanhf_(float x) {
-  // tanh(x) = 1 - 2/(exp(2x)+1); exact to ~1e-7 abs, saturates cleanly for |x| large
-  float e = __expf(2.0f * x);
-  return 1.0f - 2.0f / (e + 1.0f);
-}
 
 #define GH_KARG __attribute__((address_space(4)))
 

@@ -32,12 +32,6 @@ __device__ unsigned long long g_nt_phase[16 * 4];
 #endif
 
 __device__ __forceinline__ int nt_swz(int j) { return (0x78 >> (2 * j)) & 3; }     // {0,2,3,1}
-__device__ __forceinline__ unsigned nt_pack_bf16(float a, float b) {
-  typedef float f32x2_t __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-  const f32x2_t v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));     // v_cvt_pk_bf16_f32 (RNE)
-}
 
 // MODE 1: opt-in operand mode: fp32 storage, fragments rounded to bf16 in registers (v_cvt_pk_bf16_f32, RNE), one
 //         v_mfma_f32_16x16x16_bf16 per K tile (a lane's four k values = its float4); epilogues fp32.
@@ -271,13 +265,13 @@ gemm_nt_kernel(const Launch L_byval) {
       typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
       // pieces of a fragment's four k values as packed bf16 pairs: {hi, mid, lo} x {k0k1, k2k3}
       auto split = [](const f32x4 v, unsigned* hi, unsigned* mid, unsigned* lo) __attribute__((always_inline)) {
-        hi[0] = nt_pack_bf16(v[0], v[1]); hi[1] = nt_pack_bf16(v[2], v[3]);
+        hi[0] = pack_bf2(v[0], v[1]); hi[1] = pack_bf2(v[2], v[3]);
         const float r0 = v[0] - __builtin_bit_cast(float, hi[0] << 16), r1 = v[1] - __builtin_bit_cast(float, hi[0] & 0xffff0000u);
         const float r2 = v[2] - __builtin_bit_cast(float, hi[1] << 16), r3 = v[3] - __builtin_bit_cast(float, hi[1] & 0xffff0000u);
-        mid[0] = nt_pack_bf16(r0, r1); mid[1] = nt_pack_bf16(r2, r3);
+        mid[0] = pack_bf2(r0, r1); mid[1] = pack_bf2(r2, r3);
         const float q0 = r0 - __builtin_bit_cast(float, mid[0] << 16), q1 = r1 - __builtin_bit_cast(float, mid[0] & 0xffff0000u);
         const float q2 = r2 - __builtin_bit_cast(float, mid[1] << 16), q3 = r3 - __builtin_bit_cast(float, mid[1] & 0xffff0000u);
-        lo[0] = nt_pack_bf16(q0, q1); lo[1] = nt_pack_bf16(q2, q3);
+        lo[0] = pack_bf2(q0, q1); lo[1] = pack_bf2(q2, q3);
       };
       auto cat = [](const unsigned* x, const unsigned* y) __attribute__((always_inline)) {
         const u32x4 u = {x[0], x[1], y[0], y[1]};
@@ -309,12 +303,12 @@ gemm_nt_kernel(const Launch L_byval) {
       s16x4 ab[MI];
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) {
-        const uint2 u = make_uint2(nt_pack_bf16(a[mi][0], a[mi][1]), nt_pack_bf16(a[mi][2], a[mi][3]));
+        const uint2 u = make_uint2(pack_bf2(a[mi][0], a[mi][1]), pack_bf2(a[mi][2], a[mi][3]));
         ab[mi] = __builtin_bit_cast(s16x4, u);
       }
 #pragma unroll
       for (int i = 0; i < cnt; ++i) {
-        const uint2 u = make_uint2(nt_pack_bf16(b[i][0], b[i][1]), nt_pack_bf16(b[i][2], b[i][3]));
+        const uint2 u = make_uint2(pack_bf2(b[i][0], b[i][1]), pack_bf2(b[i][2], b[i][3]));
         const s16x4 bb = __builtin_bit_cast(s16x4, u);
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)
@@ -351,7 +345,7 @@ gemm_nt_kernel(const Launch L_byval) {
             float lo = __builtin_bit_cast(float, w[e] << 16), hi = __builtin_bit_cast(float, w[e] & 0xffff0000u);
             lo = drop_hash(drop_seed, idx + 2 * e) >= drop_thresh ? lo * drop_scale : 0.f;
             hi = drop_hash(drop_seed, idx + 2 * e + 1) >= drop_thresh ? hi * drop_scale : 0.f;
-            w[e] = nt_pack_bf16(lo, hi);
+            w[e] = pack_bf2(lo, hi);
           }
           a[mi] = __builtin_bit_cast(f32x4, w);
         } else {
@@ -379,13 +373,13 @@ gemm_nt_kernel(const Launch L_byval) {
       const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
       const unsigned b3_fo = lds0 + (unsigned)(BM * 64) + (unsigned)(wcol + l15) * 112u + (unsigned)q * 24u;
       auto split = [](const f32x4 v, unsigned* hi, unsigned* mid, unsigned* lo) __attribute__((always_inline)) {
-        hi[0] = nt_pack_bf16(v[0], v[1]); hi[1] = nt_pack_bf16(v[2], v[3]);
+        hi[0] = pack_bf2(v[0], v[1]); hi[1] = pack_bf2(v[2], v[3]);
         const float r0 = v[0] - __builtin_bit_cast(float, hi[0] << 16), r1 = v[1] - __builtin_bit_cast(float, hi[0] & 0xffff0000u);
         const float r2 = v[2] - __builtin_bit_cast(float, hi[1] << 16), r3 = v[3] - __builtin_bit_cast(float, hi[1] & 0xffff0000u);
-        mid[0] = nt_pack_bf16(r0, r1); mid[1] = nt_pack_bf16(r2, r3);
+        mid[0] = pack_bf2(r0, r1); mid[1] = pack_bf2(r2, r3);
         const float q0 = r0 - __builtin_bit_cast(float, mid[0] << 16), q1 = r1 - __builtin_bit_cast(float, mid[0] & 0xffff0000u);
         const float q2 = r2 - __builtin_bit_cast(float, mid[1] << 16), q3 = r3 - __builtin_bit_cast(float, mid[1] & 0xffff0000u);
-        lo[0] = nt_pack_bf16(q0, q1); lo[1] = nt_pack_bf16(q2, q3);
+        lo[0] = pack_bf2(q0, q1); lo[1] = pack_bf2(q2, q3);
       };
       auto cat = [](const u32x2 x, const u32x2 y) __attribute__((always_inline)) {
         const u32x4 u = {x[0], x[1], y[0], y[1]};
@@ -602,7 +596,7 @@ gemm_nt_kernel(const Launch L_byval) {
   auto st4 = [&](float* p, size_t o, const float4 v, bool bf) __attribute__((always_inline)) {
     if constexpr (MODE == 2) {
       if (bf) {
-        *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(p) + o) = make_uint2(nt_pack_bf16(v.x, v.y), nt_pack_bf16(v.z, v.w));
+        *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(p) + o) = make_uint2(pack_bf2(v.x, v.y), pack_bf2(v.z, v.w));
         return;
       }
     }
@@ -800,7 +794,7 @@ gemm_nt_kernel(const Launch L_byval) {
       auto st8 = [&](float* p, size_t o, const float4 a, const float4 b, bool bf) __attribute__((always_inline)) {
         if (bf) {
           *reinterpret_cast<uint4*>(reinterpret_cast<unsigned short*>(p) + o) =
-              make_uint4(nt_pack_bf16(a.x, a.y), nt_pack_bf16(a.z, a.w), nt_pack_bf16(b.x, b.y), nt_pack_bf16(b.z, b.w));
+              make_uint4(pack_bf2(a.x, a.y), pack_bf2(a.z, a.w), pack_bf2(b.x, b.y), pack_bf2(b.z, b.w));
         } else {
           *reinterpret_cast<float4*>(p + o) = a;
           *reinterpret_cast<float4*>(p + o + 4) = b;

@@ -27,7 +27,7 @@
     return r;
   };
   auto pp_pack = [](const float4 a, const float4 b) __attribute__((always_inline)) {
-    return pp_u32x4{nt_pack_bf16(a.x, a.y), nt_pack_bf16(a.z, a.w), nt_pack_bf16(b.x, b.y), nt_pack_bf16(b.z, b.w)};
+    return pp_u32x4{pack_bf2(a.x, a.y), pack_bf2(a.z, a.w), pack_bf2(b.x, b.y), pack_bf2(b.z, b.w)};
   };
   auto sig4 = [](const float4 v) __attribute__((always_inline)) { return make_float4(sigmoidf_(v.x), sigmoidf_(v.y), sigmoidf_(v.z), sigmoidf_(v.w)); };
   auto tanh4 = [](const float4 v) __attribute__((always_inline)) { return make_float4(tanhf_(v.x), tanhf_(v.y), tanhf_(v.z), tanhf_(v.w)); };

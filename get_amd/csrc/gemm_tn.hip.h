@@ -161,7 +161,7 @@ gemm_tn_kernel(const Launch L_byval) {
   if constexpr (BF) {
     typedef short s16x4 __attribute__((ext_vector_type(4)));
     auto pk = [](float a, float b, float c, float d) __attribute__((always_inline)) {
-      return __builtin_bit_cast(s16x4, make_uint2(nt_pack_bf16(a, b), nt_pack_bf16(c, d)));
+      return __builtin_bit_cast(s16x4, make_uint2(pack_bf2(a, b), pack_bf2(c, d)));
     };
     Frag f[4];
     for (int t = 0; t < T; ++t) {

@@ -2,8 +2,7 @@
 // fused word-scorer + GSL top-k.  All HBM-bound integer/bit work plus one streaming FMA pass;
 // no MFMA here by design.
 #include "../../include/get_hip.h"
-#include "common.h"
-#include "gemm.hip.h"
+#include "device_utils.h"
 #include <stdlib.h>
 
 namespace gh {
@@ -242,18 +241,6 @@ adj_unpack_kernel(const uint64_t* __restrict__ bits, const float* __restrict__ d
 // feature rows), the refined neighbour bit-rows and dinv sit beside it, and every output float4
 // walks its row's set bits with ctz -- each feature row leaves HBM exactly once per slab.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float4 bf4_to_f4(uint2 u) {
-  return make_float4(__builtin_bit_cast(float, u.x << 16), __builtin_bit_cast(float, u.x & 0xffff0000u),
-                     __builtin_bit_cast(float, u.y << 16), __builtin_bit_cast(float, u.y & 0xffff0000u));
-}
-__device__ __forceinline__ unsigned pack_bf2(float a, float b) {
-  typedef float f32x2_t __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-  const f32x2_t v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ uint2 f4_to_bf4(float4 v) { return make_uint2(pack_bf2(v.x, v.y), pack_bf2(v.z, v.w)); }
-
 // BF (with V = 4): x and y hold bf16 (the bf16 storage pipeline); the slab is widened to fp32 when it is staged
 template <int V, bool BF = false>   // V = 4: float4 columns, V = 1: scalar columns
 __global__ void __launch_bounds__(256)
@@ -940,7 +927,7 @@ int launch_spmm(const uint64_t* bits, const float* dinv, const float* vals, cons
   const double rows = goff ? (double)m_real : (double)n * r;
   const double alg_bytes = (2.0 + (accumulate ? 1.0 : 0.0)) * rows * h * (bf16 ? 2.0 : 4.0) +
                            (double)n * ((double)r * W * 8.0 + (vals ? (double)r * r * 4.0 : (double)r * 4.0));
-  const int ptag = n < PROF_FEW_GROUPS ? PROF_FEW_ROWS : PROF_SPMM;
+  const int ptag = few_rows_tag(n, PROF_SPMM);
   prof_begin(s, ptag);
   if (bf16 && r <= 128 && h % 8 == 0) {
     // bf16 rows: the aggregation as a dense product per graph on the matrix pipe (spmm_mfma_bf16_kernel), slabs of 128 columns,

@@ -1,0 +1,113 @@
+// The library's host-side state: the error message behind gh_last_error (set_error), the optional per-kernel event profiler
+// (prof_begin / prof_end, gh_profile_*), the per-device counters of clamped inputs (clamp_counter, gh_clamp_events) and
+// gh_abi_version.  Host code only: this file holds no kernel.
+#include "../../include/get_hip.h"
+#include "common.h"
+#include <mutex>
+#include <stdarg.h>
+#include <unordered_map>
+#include <vector>
+
+namespace gh {
+
+static thread_local char g_err[512] = "";
+
+void set_error(const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
+}
+
+// ---------------------------------------------------------------------------- event profiler
+struct ProfRec { hipEvent_t a, b; int tag; double work; };
+static bool g_prof_on = false;
+static unsigned g_prof_mask = 0xFFFFFFFFu;     // bit t set: kernels with tag t are instrumented (gh_profile_select)
+static std::vector<ProfRec> g_prof_recs;
+static std::vector<hipEvent_t> g_prof_pool;
+static hipEvent_t g_prof_cur = nullptr;
+
+static hipEvent_t prof_event() {
+  if (!g_prof_pool.empty()) { hipEvent_t e = g_prof_pool.back(); g_prof_pool.pop_back(); return e; }
+  hipEvent_t e = nullptr;
+  if (hipEventCreate(&e) != hipSuccess) return nullptr;
+  return e;
+}
+bool prof_enabled() { return g_prof_on; }
+void prof_begin(hipStream_t s, int tag) {
+  g_prof_cur = nullptr;
+  if (!g_prof_on || !((g_prof_mask >> tag) & 1u)) return;
+  g_prof_cur = prof_event();
+  if (g_prof_cur) (void)hipEventRecord(g_prof_cur, s);
+}
+void prof_end(int tag, double work, hipStream_t s) {
+  if (!g_prof_on || !g_prof_cur) return;
+  hipEvent_t b = prof_event();
+  if (!b) return;
+  (void)hipEventRecord(b, s);
+  g_prof_recs.push_back(ProfRec{g_prof_cur, b, tag, work});
+  g_prof_cur = nullptr;
+}
+
+// Device counters of clamped out-of-range inputs (include/get_hip.h gh_clamp_events): four unsigned ints per device, allocated
+// on first use, handed to the kernels that clamp (cross_entropy: [0], left_assemble: [1], evd_assemble: [2]).
+static std::mutex g_clamp_mu;
+static std::unordered_map<int, unsigned int*> g_clamp_buf;
+unsigned int* clamp_counter() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  std::lock_guard<std::mutex> lk(g_clamp_mu);
+  auto it = g_clamp_buf.find(dev);
+  if (it != g_clamp_buf.end()) return it->second;
+  unsigned int* p = nullptr;
+  if (hipMalloc((void**)&p, 4 * sizeof(unsigned int)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+  if (hipMemset(p, 0, 4 * sizeof(unsigned int)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(p); return nullptr; }
+  g_clamp_buf.emplace(dev, p);
+  return p;
+}
+
+}  // namespace gh
+
+using namespace gh;
+
+extern "C" int gh_clamp_events(int64_t* out, int reset) {
+  GH_REQUIRE(out, "clamp_events: NULL output");
+  unsigned int* p = clamp_counter();
+  GH_REQUIRE(p, "clamp_events: cannot allocate the counter");
+  unsigned int h[4] = {0, 0, 0, 0};
+  GH_CHECK_HIP(hipDeviceSynchronize());
+  GH_CHECK_HIP(hipMemcpy(h, p, sizeof(h), hipMemcpyDeviceToHost));
+  for (int i = 0; i < 4; ++i) out[i] = (int64_t)h[i];
+  if (reset) GH_CHECK_HIP(hipMemset(p, 0, sizeof(h)));
+  return 0;
+}
+
+extern "C" int gh_abi_version(void) { return GH_ABI_VERSION; }
+extern "C" const char* gh_last_error(void) { return g_err; }
+
+extern "C" int gh_profile_enable(int on) {
+  g_prof_on = on != 0;
+  return 0;
+}
+// out[PROF_NTAGS][3] = {total ms, total work, launches}; waits for the recorded events, then resets.
+extern "C" int gh_profile_select(uint32_t tag_mask) {
+  g_prof_mask = tag_mask;
+  return 0;
+}
+
+extern "C" int gh_profile_collect(double* out, int rows) {
+  GH_REQUIRE(rows >= PROF_NTAGS, "profile_collect: need %d rows", (int)PROF_NTAGS);
+  for (int i = 0; i < rows * 3; ++i) out[i] = 0.0;
+  for (auto& r : g_prof_recs) {
+    float ms = 0.f;
+    GH_CHECK_HIP(hipEventSynchronize(r.b));
+    GH_CHECK_HIP(hipEventElapsedTime(&ms, r.a, r.b));
+    out[r.tag * 3 + 0] += ms;
+    out[r.tag * 3 + 1] += r.work;
+    out[r.tag * 3 + 2] += 1.0;
+    g_prof_pool.push_back(r.a);
+    g_prof_pool.push_back(r.b);
+  }
+  g_prof_recs.clear();
+  return 0;
+}

@@ -1,6 +1,6 @@
 """Every dispatch path of the plain linear GEMMs (gh_linear_fwd / gh_linear_bwd of csrc/dense_ops.hip: the host planner `Batch` of
 csrc/gemm_ops.hip with the NT, TN and generic MFMA kernels, the split-K finish and reduce kernels, the tiny-width kernels
-and the column sums of csrc/misc_ops.hip) against float64 on the CPU, and gh_transpose / gh_transpose_batch /
+and the column sums of csrc/stream_ops.hip) against float64 on the CPU, and gh_transpose / gh_transpose_batch /
 gh_weights_refresh bit for bit.
 
 The C-ABI entries are called directly.  Every operand and every output sits inside a larger NaN-filled allocation of its

@@ -144,7 +144,7 @@ def test_unit_seed_backward_is_plain_backward_for_any_loss():
 
 
 def test_stateless_dropout_mask_is_unbiased_and_uncorrelated():
-    """Mask hygiene of the kernels' stateless dropout (gemm.hip.h drop_hash: murmur3-finalised idx * golden-ratio + seed;
+    """Mask hygiene of the kernels' stateless dropout (device_utils.h drop_hash: murmur3-finalised idx * golden-ratio + seed;
     ops.dropout_mask_reference is its host replica, wrapper.py:185-190 is the op it implements): over 1.2e7 elements the keep
     rate, the per-column and per-row keep rates, the lag-1 correlations along rows and along columns, and the correlation of
     two seeds' masks all sit within 4 sigma of an i.i.d. Bernoulli(1 - p) field."""
@@ -214,3 +214,20 @@ def test_layer_files_hold_no_kernel():
         assert "hipLaunchKernelGGL" not in text and "<<<" not in text, name
         for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', text, re.M):
             assert not re.match(r"gemm_(nt|tn).*\.hip\.h$", pathlib.PurePath(inc).name), f"{name} includes {inc}"
+
+
+def test_gemm_kernel_headers_stay_with_the_gemm_engine():
+    """The shared device helpers (dropout hash, sigmoid / tanh, bf16 pack / widen) live in device_utils.h, so nobody includes a GEMM
+    kernel header for them: a quoted include of gemm*.hip.h appears only in gemm_ops.hip, gemm_batch.h and the gemm*.hip.h files
+    themselves.  runtime_ops.hip (error state, profiler, counters) is host code: no kernel."""
+    import pathlib
+    import re
+    csrc = pathlib.Path(__file__).resolve().parent.parent / "get_amd" / "csrc"
+    sources = sorted(list(csrc.glob("*.hip")) + list(csrc.glob("*.h")))
+    assert sources
+    for src in sources:
+        allowed = src.name in ("gemm_ops.hip", "gemm_batch.h") or re.fullmatch(r"gemm.*\.hip\.h", src.name)
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', src.read_text(), re.M):
+            if re.fullmatch(r"gemm.*\.hip\.h", pathlib.PurePath(inc).name):
+                assert allowed, f"{src.name} includes {inc}"
+    assert "__global__" not in (csrc / "runtime_ops.hip").read_text()
