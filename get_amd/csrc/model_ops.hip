@@ -70,7 +70,7 @@ static int make_dims(const gh_get_model* Mo, const gh_get_batch* Ba, Dims& d) {
   }
   d.Mq = d.B * d.L;
   d.fuse_scorer = d.H <= 320;
-  // same rule as the per-module path (get_amd/ops.py bf16_cell_ok): 16-byte bf16 rows and activation-sized launches
+  // same rule as the per-module path (get_amd/ops/graph.py bf16_cell_ok): 16-byte bf16 rows and activation-sized launches
   d.bf = Mo->storage == 1 && d.D % 8 == 0 && d.H % 8 == 0 && d.Mr >= 8192;
   if (d.bf) {
     const gh_cell_bf16* cs[2] = {&Mo->cell1_16, &Mo->cell2_16};

@@ -245,7 +245,7 @@ class FlatTrainer:
             p.data = self.flat_p[off:off + n].view_as(p)
             gv = self.flat_g[off:off + n].view_as(p)
             p.grad = gv
-            p._gh_direct_grad = True          # kernels may accumulate straight into this view (ops._direct)
+            p._gh_direct_grad = True          # kernels may accumulate straight into this view (ops.weights._direct)
             self._views.append(gv)
             off += slot(p)
         self.numel = total

@@ -2,7 +2,7 @@
 
 ``Graph_basedSemantiStructure.forward`` routes through :func:`forward` whenever the model/batch qualify (frozen word
 table, float4-shaped widths with d <= h <= 1024 -- every shape BASELINE.json names, in every arithmetic mode incl. the
-bf16 storage pipeline of configs[4]); anything else keeps the module-by-module path of get_amd/modules.py + get_amd/ops.py, which stays the API for callers that use
+bf16 storage pipeline of configs[4]); anything else keeps the module-by-module path of get_amd/modules.py + get_amd/ops/, which stays the API for callers that use
 the reference's modules one by one.  Same kernels underneath; what disappears is ~120 Python -> ctypes -> autograd round
 trips per training step (~2.2 ms of host time, the bound of the realistic-evidence-count regime) and the at::native
 glue between them.
@@ -145,7 +145,7 @@ class Binding:
                 raise RuntimeError(f"get_amd: struct layout mismatch between fused.py {mine} and libget_hip.so {tuple(sz)}")
             self._checked = True
         m = self.model
-        direct = need_grads and all(ops._direct(p) for p in self.params) and all((not t.requires_grad) or ops._direct(t) for t in self.tables)
+        direct = need_grads and all(ops.weights._direct(p) for p in self.params) and all((not t.requires_grad) or ops.weights._direct(t) for t in self.tables)
         wts = [ops.transposed(w) for w in self.mats] if need_grads else None
         gscorer = m.ggnn_with_gsl._gate12()
         # bf16 storage mode (BASELINE configs[4]): bf16 twins of the two evidence cells' matrices (persistent buffers, refreshed
@@ -469,9 +469,9 @@ class _GetFused(torch.autograd.Function):
             return (None, None, None) + (None,) * len(ctx.anchor_ids)
         if g_phi is None:
             g_phi = torch.zeros((prep.b, prep.c), device=dev, dtype=torch.float32)
-        g_phi = ops._f32(g_phi)
-        g_word_w = ops._f32(g_word_w) if g_word_w is not None else None      # loss terms on the attention weights
-        g_evd_w = ops._f32(g_evd_w) if g_evd_w is not None else None
+        g_phi = ops._util._f32(g_phi)
+        g_word_w = ops._util._f32(g_word_w) if g_word_w is not None else None      # loss terms on the attention weights
+        g_evd_w = ops._util._f32(g_evd_w) if g_evd_w is not None else None
         M, direct, gbuf, views = binding.get(True)
         main = _lib.stream()
         side_raw = side.cuda_stream if side is not None else main
@@ -495,7 +495,9 @@ class _GetFused(torch.autograd.Function):
             # the claim branch is final in stream order after phase 1 -- the early all-reduce starts underneath phase 2
             _lib.call("gh_get_backward", *args, 1, main, side_raw)
             if side is not None:
-                ops._side_pending.add(dev.index if dev.index is not None else torch.cuda.current_device())
+                # no join callback: phase 2 of gh_get_backward joins the streams itself.  The mark only lets
+                # pending_side_stream() tell the hook's all-reduce about the work still running on the side stream
+                ops.streams._mark_pending(ops.streams._index(dev), False)
             try:
                 hook()
             except BaseException:
@@ -543,12 +545,12 @@ def forward(model, query, document, kargs):
     if plan is None and AUTO_COMPACT and not isinstance(kargs[K.Evd_Docs_Adj], PackedAdj):
         plan = _plan_from_dense(d_adj, doc)
     prep = _prepare(model, query, document, kargs, q_adj, d_adj, plan, doc)
-    side = ops.side_stream(query.device) if ops.CLAIM_SIDE_STREAM else None
+    side = ops.side_stream(query.device) if ops.streams.CLAIM_SIDE_STREAM else None
     # anchors: the tensors autograd tracks.  With a FlatTrainer every gradient lands in the bucket directly, so ONE
     # parameter is enough to keep the graph connected; otherwise all live parameters are inputs and get their gradients
     # back from the backward call.
     params = binding.params + [t for t in binding.tables if t.requires_grad]
-    if torch.is_grad_enabled() and all(ops._direct(p) for p in params):
+    if torch.is_grad_enabled() and all(ops.weights._direct(p) for p in params):
         anchors = (params[-1],)
     else:
         anchors = tuple(params)
@@ -587,7 +589,7 @@ class _CrossEntropy(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, phi, labels):
-        phi = ops._f32(phi)
+        phi = ops._util._f32(phi)
         b, c = phi.shape
         labels = labels.to(torch.int64).contiguous()
         out = torch.empty(1 + b * c, device=phi.device, dtype=torch.float32)

@@ -916,7 +916,7 @@ class Graph_basedSemantiStructure(nn.Module):
         # the word attention: on a ROCm device it runs on a side stream underneath the evidence cells' GEMMs.  It is
         # issued AFTER the evidence branch so that autograd (which replays nodes newest-first, each on its forward
         # stream) also starts the claim backward before the evidence cells' backward.
-        side = ops.side_stream(query.device) if ops.CLAIM_SIDE_STREAM and query.is_cuda else None
+        side = ops.side_stream(query.device) if ops.streams.CLAIM_SIDE_STREAM and query.is_cuda else None
         if side is None:
             q_repr, query_repr = claim_branch()
         else:
@@ -940,7 +940,7 @@ class Graph_basedSemantiStructure(nn.Module):
             query_repr.record_stream(main)
             if query_repr.requires_grad:
                 # the claim branch's backward will run on the side stream: join it at the end of the backward pass
-                # whether or not any other side-stream work (ops._side_wgrad) happens in that pass
+                # whether or not any other side-stream work (ops.streams._side_wgrad) happens in that pass
                 dev_ = query.device
                 query_repr.register_hook(lambda g, _d=dev_: ops.side_mark_backward(_d))
 

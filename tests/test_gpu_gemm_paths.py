@@ -546,3 +546,30 @@ def test_weights_refresh_of_no_matrix_writes_nothing():
     torch.cuda.synchronize()
     f.check("weights_refresh n = 0")
     assert bool(torch.isnan(wt).all())
+
+
+@pytest.mark.parametrize("shape", [(5, 7), (8, 12)])
+def test_weight_caches_serve_exact_copies_and_keep_their_addresses(shape):
+    """ops.transposed and ops.bf16_twins over the kernels above: exact copies, a hit is the same object, an in-place update is
+    seen, and a refresh rewrites the twins where they are (the kernels themselves: test_weights_refresh_with_bf16_twins)."""
+    _, ops = _ops()
+    ops.bump_weight_epoch()
+    w = torch.nn.Parameter(torch.randn(shape, device="cuda"))
+    wt = ops.transposed(w)
+    _exact(wt, w.detach().t().contiguous(), "transposed")
+    assert ops.transposed(w) is wt
+    with torch.no_grad():
+        w.add_(1)
+    _exact(ops.transposed(w), w.detach().t().contiguous(), "transposed after an in-place update")
+    w16, wt16 = ops.bf16_twins(w)
+    _exact(w16, w.detach().to(torch.bfloat16), "bf16 twin")
+    _exact(wt16, w.detach().t().contiguous().to(torch.bfloat16), "bf16 twin of the transpose")
+    addresses = (w16.data_ptr(), wt16.data_ptr())
+    with torch.no_grad():
+        w.mul_(0.5)
+    ops.refresh_transposes([w])
+    again = ops.bf16_twins(w)
+    assert (again[0].data_ptr(), again[1].data_ptr()) == addresses
+    _exact(again[0], w.detach().to(torch.bfloat16), "bf16 twin after the refresh")
+    _exact(again[1], w.detach().t().contiguous().to(torch.bfloat16), "bf16 twin of the transpose after the refresh")
+    _exact(ops.transposed(w), w.detach().t().contiguous(), "transposed after the refresh")

@@ -97,7 +97,7 @@ def test_claim_side_stream_is_bit_identical_to_single_stream(native, monkeypatch
     from get_amd import ops
     runs = {}
     for side in (False, True, True, False):
-        monkeypatch.setattr(ops, "CLAIM_SIDE_STREAM", side)
+        monkeypatch.setattr(ops.streams, "CLAIM_SIDE_STREAM", side)
         cfg, model, inp, phi, ww, ew, loss = run_case("small", native_graphs=native)
         loss.backward()
         torch.cuda.synchronize()
@@ -114,7 +114,7 @@ def test_claim_side_stream_is_bit_identical_to_single_stream(native, monkeypatch
 
 def test_side_stream_weight_gradients_are_bit_identical(monkeypatch):
     """With a FlatTrainer the weight gradients of the evidence-level attention and the head are issued on the auxiliary
-    stream and joined when backward ends (ops._side_wgrad): the flat gradient bucket must equal the in-line schedule bit
+    stream and joined when backward ends (ops.streams._side_wgrad): the flat gradient bucket must equal the in-line schedule bit
     for bit, read right after backward() on the caller's stream, several times in a row."""
     from get_amd import ops
     from get_amd.dist import FlatTrainer
@@ -125,7 +125,7 @@ def test_side_stream_weight_gradients_are_bit_identical(monkeypatch):
     raw = make_raw_batch(cfg, MODEL_CASES["small"][1])
     buckets = {}
     for side in (False, True, True, False, True):
-        monkeypatch.setattr(ops, "WGRAD_SIDE_STREAM", side)
+        monkeypatch.setattr(ops.streams, "WGRAD_SIDE_STREAM", side)
         trainer.zero_grad()
         cfg2, model2, inp2, phi2, ww2, ew2, loss2 = None, None, None, None, None, None, None
         query = torch.from_numpy(inp["query"]).to(DEV)
@@ -903,7 +903,7 @@ def test_native_batch_counts_nodes_like_convert_text():
 
 def test_claim_branch_backward_on_the_side_stream_is_joined_without_side_wgrad(monkeypatch):
     """with a FlatTrainer the claim cell's backward writes straight into the flat bucket and returns nothing to
-    autograd, so the engine never joins the auxiliary stream it ran on; the only join used to come from ops._side_wgrad.
+    autograd, so the engine never joins the auxiliary stream it ran on; the only join used to come from ops.streams._side_wgrad.
     With GET_AMD_WGRAD_STREAM off nothing ordered those writes against the caller's stream.  Made deterministic here: the
     side stream is kept busy for ~100 ms before backward(), so the claim backward is still pending when backward()
     returns -- the bucket read on the caller's stream right after must nevertheless be complete."""
@@ -913,7 +913,7 @@ def test_claim_branch_backward_on_the_side_stream_is_joined_without_side_wgrad(m
     trainer = FlatTrainer(model, lr=1e-4, weight_decay=1e-3)
     ops.bump_weight_epoch()
     model.train(False)
-    monkeypatch.setattr(ops, "WGRAD_SIDE_STREAM", False)
+    monkeypatch.setattr(ops.streams, "WGRAD_SIDE_STREAM", False)
     query = torch.from_numpy(inp["query"]).to(DEV)
     document = torch.from_numpy(inp["document"]).to(DEV)
     labels = torch.from_numpy(inp["labels"]).to(DEV)
@@ -1162,7 +1162,7 @@ def test_fp32x3_linear_is_fp32_accurate_and_follows_weight_updates(x3_mode, m, k
     ops.bump_weight_epoch()
     check()
     w.data.add_(0.25)                 # a raw-pointer style update: no _version bump, the trainer's calls announce it
-    ops._bump_trainer_epoch()
+    ops.weights._bump_trainer_epoch()
     ops.refresh_transposes([w])       # (transposes first, then -- in the pre-split mode -- every image in one launch)
     check()
 

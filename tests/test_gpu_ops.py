@@ -549,13 +549,13 @@ def test_spmm_bf16_is_the_fp32_aggregation_rounded_once(h, n_graphs, window):
             for tr, acc in ((0, 0), (1, 1)):
                 x32 = xin.float().contiguous()
                 y32 = yin.float().contiguous() if acc else torch.empty_like(x32)
-                _lib.call("gh_spmm", *a._args(), *ops._plan_args(pl), _lib.ptr(x32), _lib.ptr(y32), n, r, h, tr, acc, _lib.stream())
+                _lib.call("gh_spmm", *a._args(), *ops.graph._plan_args(pl), _lib.ptr(x32), _lib.ptr(y32), n, r, h, tr, acc, _lib.stream())
                 y16 = yin.clone() if acc else torch.empty_like(xin)
-                _lib.call("gh_spmm_bf16", *a._args(), *ops._plan_args(pl), _lib.ptr(xin), _lib.ptr(y16), n, r, h, tr, acc, _lib.stream())
+                _lib.call("gh_spmm_bf16", *a._args(), *ops.graph._plan_args(pl), _lib.ptr(xin), _lib.ptr(y16), n, r, h, tr, acc, _lib.stream())
                 torch.cuda.synchronize()
                 # scale of the sum: the same aggregation of |x| (the weights are positive), plus |y| when accumulating
                 s32 = yin.float().abs().contiguous() if acc else torch.empty_like(x32)
-                _lib.call("gh_spmm", *a._args(), *ops._plan_args(pl), _lib.ptr(x32.abs().contiguous()), _lib.ptr(s32), n, r, h, tr, acc, _lib.stream())
+                _lib.call("gh_spmm", *a._args(), *ops.graph._plan_args(pl), _lib.ptr(x32.abs().contiguous()), _lib.ptr(s32), n, r, h, tr, acc, _lib.stream())
                 torch.cuda.synchronize()
                 want = y32.to(torch.bfloat16)
                 # (1) against the fp32 sum: half a bf16 ulp of the result + fp32-level error of the sum (cancelling sums included)
