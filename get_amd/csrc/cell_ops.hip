@@ -185,7 +185,7 @@ int gh::cell_bwd_impl(int bf, const uint64_t* bits, const float* dinv, const flo
                                 float* dw_h0, float* dw_h1, float* db_z, float* db_r, float* db_h,
                                 float* db_z1, float* db_r1, float* db_h1, float drop_p, uint32_t drop_seed,
                                 gh_stream_t stream, gh_stream_t wstream, hipEvent_t ev_l1, hipEvent_t ev_agg,
-                                int pre_done, const GateFuse* next, const float* xdrop) {
+                                int pre_done, const GateFuse* next, const float* xdrop, float* ybuf, int nodx_ok) {
   hipStream_t s = (hipStream_t)stream;
   // Weight-gradient stream (composite backward, model_ops.hip): the split-K weight-gradient GEMMs only need dzp / drp / dhp
   // (final after the first dX launch) and, for dW_proj, dxp (final after the aggregation).  On their own stream they run
@@ -208,6 +208,94 @@ int gh::cell_bwd_impl(int bf, const uint64_t* bits, const float* dinv, const flo
   if (!pre_done)
     if (int e = launch_gate_bwd_pre(g, z, hh, xp, dhp, dzp, dxp, (size_t)M * h, s, bf)) return e;
   const bool wide = bf && h % 256 == 0;
+  // No input gradient leaves this cell (frozen embeddings behind ids, or an input that needs none): da and the full dxp would
+  // only feed dW_p.  With X the masked, gathered input rows, Y = A_hat X (so a = Y Wp^T, xp = X Wp^T) and E = dxp after the
+  // d(r xp) product, the weight gradients re-associate:
+  //     T_g = G_g^T Y (g = z, r, h), S_g = G_g^T X (g = z, r)            five h x din outputs over the M rows
+  //     dW_g0 = T_g Wp^T,  dW_g1 = S_g Wp^T,  dW_p = E^T X + Wz1^T S_z + Wr1^T S_r + sum_g W_g0^T T_g
+  // Four of the five activation-sized NT products (da from three gates, dxp from two) are gone, the aggregation moves from da
+  // to X, and ten weight-sized products (launch_nn_accumulate) finish the job.  T / S live in the tail of the stream's split-K
+  // workspace, which the weight-gradient launches are told not to use.
+  const size_t ts_floats = 5 * (size_t)h * (size_t)din;
+  const Workspace wsp = workspace_for(s);
+  const bool nodx = nodx_ok && !dx && !next && !bf && !two && din <= h && din % 4 == 0 && h % 4 == 0 && wsp.p != nullptr &&
+                    (reinterpret_cast<uintptr_t>(wsp.p) & 15) == 0 && wsp.bytes / 2 >= ts_floats * sizeof(float);
+  if (nodx) {
+    const size_t hd = (size_t)h * (size_t)din;
+    float* ts = wsp.p + wsp.bytes / sizeof(float) - ts_floats;      // (wsp.bytes and 20 h din are multiples of 16)
+    float *t_z = ts, *t_r = ts + hd, *t_h = ts + 2 * hd, *s_z = ts + 3 * hd, *s_r = ts + 4 * hd;
+    const size_t ws_left = wsp.bytes - ts_floats * sizeof(float);
+    {  // d(r xp) = dhp Wh1 -> drp, dxp += .   (no da)
+      Batch b(false, M, s, false, SITE_CELL_BWD_H, h);
+      Problem p1 = gemm_problem(M, h, EPI_BWD_DRX, drp, h, dhp, h, wt_h1, h, h);
+      p1.out1 = dxp; p1.in0 = xp; p1.in1 = rr;
+      b.add(p1);
+      b.flush();
+      GH_CHECK_HIP(b.err);
+    }
+    const float* X = x;
+    if (ids || drop_p > 0.f) {      // embedding gather and / or the forward's dropout mask, once, into the free `da` scratch
+      if (int e = launch_gather_rows(x, ids, da, M, din, s, drop_p, drop_seed, 0)) return e;
+      X = da;
+    }
+    bool cs_ok = false;
+    auto add_s = [&](Batch& b) {      // the problems that read X and E
+      b.add(tn_problem(h, din, s_z, din, dzp, h, X, din, M));  if (!ybuf) b.want_colsum(db_z, db_z1);
+      b.add(tn_problem(h, din, s_r, din, drp, h, X, din, M));  if (!ybuf) b.want_colsum(db_r, db_r1);
+      b.add(tn_problem(h, h, dw_h1, h, dhp, h, rx, h, M));     if (!ybuf) b.want_colsum(db_h, db_h1);
+      b.add(tn_problem(h, din, dw_p, din, dxp, h, X, din, M));
+    };
+    if (ybuf) {  // one weight-gradient launch; the zero fill of T / S rides on the aggregation
+      ZeroFill zf = {ts, (long long)ts_floats, nullptr, 0};
+      bool zf_done = false;
+      if (int e = launch_spmm(bits, dinv, vals, keep, goff, m_real, X, ybuf, n, r, din, 0, 0, s, 0, &zf, &zf_done)) return e;   // Y = A_hat X
+      if (!zf_done) GH_CHECK_HIP(hipMemsetAsync(ts, 0, ts_floats * sizeof(float), s));
+      Batch b(true, M, s);
+      b.g_ws_bytes = ws_left;
+      b.add(tn_problem(h, din, t_z, din, dzp, h, ybuf, din, M));  b.want_colsum(db_z, db_z1);
+      b.add(tn_problem(h, din, t_r, din, drp, h, ybuf, din, M));  b.want_colsum(db_r, db_r1);
+      b.add(tn_problem(h, din, t_h, din, dhp, h, ybuf, din, M));  b.want_colsum(db_h, db_h1);
+      add_s(b);
+      b.flush();
+      GH_CHECK_HIP(b.err);
+      cs_ok = b.colsum_fused && !b.colsum_missed;
+    } else {     // no second row buffer: X and E first, then Y takes the place of dxp
+      GH_CHECK_HIP(hipMemsetAsync(ts, 0, ts_floats * sizeof(float), s));
+      Batch b(true, M, s);
+      b.g_ws_bytes = ws_left;
+      add_s(b);
+      b.flush();
+      GH_CHECK_HIP(b.err);
+      cs_ok = b.colsum_fused && !b.colsum_missed;
+      if (int e = launch_spmm(bits, dinv, vals, keep, goff, m_real, X, dxp, n, r, din, 0, 0, s, 0)) return e;   // Y = A_hat X
+      Batch b2(true, M, s);
+      b2.g_ws_bytes = ws_left;
+      b2.add(tn_problem(h, din, t_z, din, dzp, h, dxp, din, M));
+      b2.add(tn_problem(h, din, t_r, din, drp, h, dxp, din, M));
+      b2.add(tn_problem(h, din, t_h, din, dhp, h, dxp, din, M));
+      b2.flush();
+      GH_CHECK_HIP(b2.err);
+    }
+    NnArgs R;
+    memset(&R, 0, sizeof(R));
+    R.n = 6;
+    NnItem& ip = R.it[0];      // dW_p first: five terms, its tiles run longest
+    ip.C = dw_p; ip.I = h; ip.J = din; ip.ldc = din;
+    nn_add_term(ip, wt_z0, h, t_z, din, h);
+    nn_add_term(ip, wt_r0, h, t_r, din, h);
+    nn_add_term(ip, wt_h0, h, t_h, din, h);
+    nn_add_term(ip, wt_z1, h, s_z, din, h);
+    nn_add_term(ip, wt_r1, h, s_r, din, h);
+    float* const dwg[5] = {dw_z0, dw_r0, dw_h0, dw_z1, dw_r1};
+    for (int i = 0; i < 5; ++i) {      // dW_g0 = T_g Wp^T, dW_g1 = S_g Wp^T (wt_p = Wp^T as stored, [din][h])
+      NnItem& it = R.it[1 + i];
+      it.C = dwg[i]; it.I = h; it.J = h; it.ldc = h;
+      nn_add_term(it, ts + i * hd, din, wt_p, h, din);
+    }
+    if (int e = launch_nn_accumulate(R, s)) return e;
+    if (cs_ok) return 0;
+    return launch_colsum3(dzp, drp, dhp, db_z, db_r, db_h, M, h, s, db_z1, db_r1, db_h1);
+  }
   {  // hp = a Wh0^T + (r xp) Wh1^T:  da = dhp Wh0 ; d(r xp) = dhp Wh1 -> drp, dxp += .
     Batch b(false, M, s, wide, SITE_CELL_BWD_H, h);
     Problem p0 = gemm_problem(M, h, EPI_STORE, da, h, dhp, h, wt_h0, h, h, nullptr, bf);
@@ -313,7 +401,7 @@ extern "C" int gh_ggnn_cell_bwd(const uint64_t* bits, const float* dinv, const f
                                 gh_stream_t stream) {
   return cell_bwd_impl(0, bits, dinv, vals, keep, goff, m_real, x, ids, n, r, din, h, wt_p, wt_z0, wt_z1, wt_r0, wt_r1, wt_h0, wt_h1,
                        xp, a, z, rr, rx, hh, g, dhp, dzp, drp, dxp, da, dx, dw_p, dw_z0, dw_z1, dw_r0, dw_r1, dw_h0, dw_h1,
-                       db_z, db_r, db_h, db_z1, db_r1, db_h1, drop_p, drop_seed, stream, nullptr, nullptr, nullptr, 0, nullptr, nullptr);
+                       db_z, db_r, db_h, db_z1, db_r1, db_h1, drop_p, drop_seed, stream, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 1);
 }
 
 extern "C" int gh_ggnn_cell_bwd_bf16(const uint64_t* bits, const float* dinv, const float* vals, const uint64_t* keep,
@@ -333,5 +421,5 @@ extern "C" int gh_ggnn_cell_bwd_bf16(const uint64_t* bits, const float* dinv, co
   return cell_bwd_impl(1, bits, dinv, vals, keep, goff, m_real, (cf)x, ids, n, r, din, h, (cf)wt_p, (cf)wt_z0, (cf)wt_z1, (cf)wt_r0,
                        (cf)wt_r1, (cf)wt_h0, (cf)wt_h1, (cf)xp, (cf)a, (cf)z, (cf)rr, (cf)rx, (cf)hh, g, (mf)dhp, (mf)dzp, (mf)drp,
                        (mf)dxp, (mf)da, dx, dw_p, dw_z0, dw_z1, dw_r0, dw_r1, dw_h0, dw_h1, db_z, db_r, db_h, db_z1, db_r1,
-                       db_h1, drop_p, drop_seed, stream, nullptr, nullptr, nullptr, 0, nullptr, nullptr);
+                       db_h1, drop_p, drop_seed, stream, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 1);
 }

@@ -162,7 +162,11 @@ int cell_bwd_impl(int bf, const uint64_t* bits, const float* dinv, const float* 
                   void* wstream, hipEvent_t ev_l1, hipEvent_t ev_agg,       // wstream: weight-gradient stream (NULL = stream)
                   int pre_done, const GateFuse* next,    // pre_done: dhp / dzp / dxp already hold the gate head (skip gate_bwd_pre);
                                                          // next: write the dX product into the previous cell's gate head instead of dx
-                  const float* xdrop = nullptr);         // the forward's masked operand rows (cell_fwd_impl xdrop), or NULL
+                  const float* xdrop = nullptr,          // the forward's masked operand rows (cell_fwd_impl xdrop), or NULL
+                  float* ybuf = nullptr,                 // optional scratch [m_real][din] fp32 for the no-input-gradient branch (A_hat X);
+                                                         // without it that branch re-uses dxp and takes two weight-gradient launches
+                  int nodx_ok = 1);                      // 0: keep the da / dxp chain even where that branch applies (few-row calls: its
+                                                         // ten weight-sized products outweigh the five row products it removes below ~2 din rows)
 int att_fwd_impl(const float* left, int nl, const int32_t* rowu, const float* right, const float* mask, const int32_t* goff,
                  const int32_t* rowg, int m_real, int b, int l, int xl, int dr, int ha, int heads, const float* w1, const float* w2,
                  float* u, float* t, float* e, float* weights, float* attended, hipStream_t s, int u_mode = 0,

@@ -80,6 +80,17 @@ int launch_att_finish(float* t, const float* u, const float* w2, float* e, const
 // out [I][J] += the sum of n_parts partials [I][J] stored I * J floats apart (J % 4 == 0): few outputs, many partials -- one wave
 // per float4 (reduce_partials_wave_kernel)
 int launch_reduce_wave(const float* parts, int n_parts, float* out, int I, int J, hipStream_t s);
+// Weight-sized NN products, all row-major: C [I][J] += sum over the item's terms of A_t [I][K_t] . B_t [K_t][J].  The cell
+// backward's fix-up of its re-associated weight gradients (cell_ops.hip): ten 300^3 products in one launch, every output tile
+// owned by one workgroup that adds its K chunks in a fixed order -- no atomics (nn_accumulate_kernel).
+constexpr int NN_MAX_TERMS = 5, NN_MAX_ITEMS = 6;
+struct NnTerm { const float* A; const float* B; int lda, ldb, K, vec; };      // vec: filled in by the launcher (16-byte loads of A)
+struct NnItem { float* C; int I, J, ldc, nterm, tile0; NnTerm t[NN_MAX_TERMS]; };      // tile0: filled in by the launcher
+struct NnArgs { NnItem it[NN_MAX_ITEMS]; int n; };
+inline void nn_add_term(NnItem& it, const float* A, int lda, const float* B, int ldb, int K) {
+  it.t[it.nterm++] = NnTerm{A, B, lda, ldb, K, 0};
+}
+int launch_nn_accumulate(NnArgs& R, hipStream_t s);      // (items with the most terms first: their tiles run longest)
 
 inline Problem gemm_problem(int M, int N, int epi, float* C, int ldc, const float* A, int lda, const float* B, int ldb,
                             int K, const int32_t* gatherA = nullptr, int elt = 0) {

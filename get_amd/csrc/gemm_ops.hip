@@ -389,6 +389,106 @@ reduce_partials_wave_kernel(const ReduceArgs R) {
   }
 }
 
+// C [I][J] += sum_t A_t [I][K_t] . B_t [K_t][J] on weight-sized operands (gemm_batch.h NnArgs).  One workgroup of eight waves
+// per 32 x 32 output tile; the 16-deep K chunks of the item's concatenated terms are dealt round-robin to the waves.  No LDS
+// stage: with lane group q = lane / 16 taking k = k0 + 4 q + s in MFMA step s (any assignment of k to steps and groups is a valid
+// contraction as long as A and B agree on it), a lane's four A values are ONE 16-byte load of its row and its B values four
+// loads that 16 lanes coalesce, so a chunk is ten independent loads and sixteen v_mfma_f32_16x16x4_f32 per wave.  The eight
+// partial tiles are added in wave order: fixed summation order, every output element has one writer.  (First version, FMAs on
+// 4 x 4 register blocks over an LDS stage with two barriers per chunk: 184 us for the ten 300^3 products of a cell backward --
+// launch-sized work is latency-bound, not FLOP-bound.)
+constexpr int NN_T = 32, NN_K = 16, NN_WAVES = 8;
+__global__ void __launch_bounds__(64 * NN_WAVES)
+nn_accumulate_kernel(const NnArgs R_byval) {
+  // (the item and term tables are indexed at run time: read them from the kernarg segment, as gemm_kernel does)
+  (void)R_byval;
+  const GH_KARG NnArgs& R = *(const GH_KARG NnArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  __shared__ float red[NN_WAVES][NN_T][NN_T];
+  int item = 0;
+  while (item + 1 < R.n && (int)blockIdx.x >= R.it[item + 1].tile0) ++item;
+  const GH_KARG NnItem& it = R.it[item];
+  const int I = it.I, J = it.J;
+  const int tiles_j = (J + NN_T - 1) / NN_T;
+  const int tile = (int)blockIdx.x - it.tile0;
+  const int i0 = (tile / tiles_j) * NN_T, j0 = (tile % tiles_j) * NN_T;
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int l15 = lane & 15, q = lane >> 4;
+  int total = 0;
+  for (int t = 0; t < it.nterm; ++t) total += (it.t[t].K + NN_K - 1) / NN_K;
+  // rows / columns beyond the matrix are clamped to its last one: their products land in accumulators that are never stored
+  int row[2], col[2];
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    row[m] = i0 + m * 16 + l15; if (row[m] > I - 1) row[m] = I - 1;
+    col[m] = j0 + m * 16 + l15; if (col[m] > J - 1) col[m] = J - 1;
+  }
+  f32x4 acc[2][2];
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+  int t = 0, base = 0;
+  for (int c = w; c < total; c += NN_WAVES) {
+    for (;;) {      // (c < total: the term is found before t runs off the table)
+      const int nc = (it.t[t].K + NN_K - 1) / NN_K;
+      if (c < base + nc) break;
+      base += nc; ++t;
+    }
+    const GH_KARG NnTerm& tm = it.t[t];
+    const float* A = tm.A;
+    const float* B = tm.B;
+    const int K = tm.K, lda = tm.lda, ldb = tm.ldb;
+    const int kk = (c - base) * NN_K + 4 * q;
+    float av[2][4], bv[2][4];
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) {
+      const float* ap = A + (size_t)row[mi] * lda + kk;
+      if (tm.vec) {      // K % 4 == 0: the four values are inside the row together or not at all
+        const float4 v = kk < K ? *reinterpret_cast<const float4*>(ap) : make_float4(0.f, 0.f, 0.f, 0.f);
+        av[mi][0] = v.x; av[mi][1] = v.y; av[mi][2] = v.z; av[mi][3] = v.w;
+      } else {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) av[mi][s] = kk + s < K ? ap[s] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) bv[ni][s] = kk + s < K ? B[(size_t)(kk + s) * ldb + col[ni]] : 0.f;
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mi][s], bv[ni][s], acc[mi][ni], 0, 0, 0);
+  }
+  // accumulator register `reg` of lane (q, l15) is element (4 q + reg, l15) of its 16 x 16 block
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) red[w][mi * 16 + 4 * q + reg][ni * 16 + l15] = acc[mi][ni][reg];
+  __syncthreads();
+  if (threadIdx.x >= NN_T * NN_T / 4) return;
+  const int ri = threadIdx.x >> 3, rj = 4 * (threadIdx.x & 7);
+  float4 sum = *reinterpret_cast<const float4*>(&red[0][ri][rj]);
+#pragma unroll
+  for (int v = 1; v < NN_WAVES; ++v) {
+    const float4 p = *reinterpret_cast<const float4*>(&red[v][ri][rj]);
+    sum.x += p.x; sum.y += p.y; sum.z += p.z; sum.w += p.w;
+  }
+  const int gi = i0 + ri, gj = j0 + rj;
+  if (gi < I) {
+    float* o = it.C + (size_t)gi * it.ldc + gj;
+    const float sv[4] = {sum.x, sum.y, sum.z, sum.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (gj + e < J) o[e] += sv[e];      // += : gradients accumulate into the caller's buffer
+  }
+}
+
 // Second half of an NT GEMM that was split over K: sum the partial tiles, then apply the problem's real epilogue
 // (any of gemm.hip.h's row epilogues).  One wave per output row.
 struct FinishItem {
@@ -812,6 +912,23 @@ int launch_reduce_wave(const float* parts, int n_parts, float* out, int I, int J
   R.n = 1;
   R.it[0] = ReduceItem{parts, out, I, J, J, n_parts, (long long)I * J};
   hipLaunchKernelGGL(reduce_partials_wave_kernel, dim3((I * (J / 4) + 3) / 4, 1), dim3(256), 0, s, R);
+  GH_LAUNCH_CHECK();
+  return 0;
+}
+int launch_nn_accumulate(NnArgs& R, hipStream_t s) {
+  GH_REQUIRE(R.n > 0 && R.n <= NN_MAX_ITEMS, "nn_accumulate: %d items", R.n);
+  int tiles = 0;
+  for (int i = 0; i < R.n; ++i) {
+    NnItem& it = R.it[i];
+    GH_REQUIRE(it.C && it.I > 0 && it.J > 0 && it.ldc >= it.J && it.nterm > 0 && it.nterm <= NN_MAX_TERMS, "nn_accumulate: bad item %d", i);
+    for (int t = 0; t < it.nterm; ++t)
+      GH_REQUIRE(it.t[t].A && it.t[t].B && it.t[t].K > 0 && it.t[t].lda >= it.t[t].K && it.t[t].ldb >= it.J, "nn_accumulate: bad term %d of item %d", t, i);
+    for (int t = 0; t < it.nterm; ++t)
+      it.t[t].vec = (reinterpret_cast<uintptr_t>(it.t[t].A) & 15) == 0 && it.t[t].lda % 4 == 0 && it.t[t].K % 4 == 0;
+    it.tile0 = tiles;
+    tiles += ((it.I + NN_T - 1) / NN_T) * ((it.J + NN_T - 1) / NN_T);
+  }
+  hipLaunchKernelGGL(nn_accumulate_kernel, dim3(tiles), dim3(64 * NN_WAVES), 0, s, R);
   GH_LAUNCH_CHECK();
   return 0;
 }

@@ -367,7 +367,7 @@ static int cell_fwd(const gh_cell_params& c, const gh_cell_bf16* c16, const Cell
 static int cell_bwd(const gh_cell_params& c, const gh_cell_bf16* c16, const CellBuf& cb, const float* A, const uint64_t* bits, const float* dinv,
                     const float* vals, const uint64_t* keep, const int32_t* goff, int m_real, const float* x, const int32_t* ids, int n,
                     int r, int din, int h, const float* g, float* W, const int64_t* sc, float* dx, float drop_p, uint32_t seed,
-                    hipStream_t s, int pre_done = 0, const GateFuse* next = nullptr) {
+                    hipStream_t s, int pre_done = 0, const GateFuse* next = nullptr, float* ybuf = nullptr, int nodx_ok = 1) {
   GH_REQUIRE(c.dw_p && c.db_z0 && c.db_z1, "get_backward: a cell's gradient outputs are missing");
   if (c16) {
     typedef const float* cf;
@@ -383,7 +383,8 @@ static int cell_bwd(const gh_cell_params& c, const gh_cell_bf16* c16, const Cell
   return cell_bwd_impl(0, bits, dinv, vals, keep, goff, m_real, x, ids, n, r, din, h, c.wt_p, c.wt_z0, c.wt_z1, c.wt_r0, c.wt_r1,
                        c.wt_h0, c.wt_h1, A + cb.xp, A + cb.a, A + cb.z, A + cb.rr, A + cb.rx, A + cb.hh, g, W + sc[0], W + sc[1],
                        W + sc[2], W + sc[3], W + sc[4], dx, c.dw_p, c.dw_z0, c.dw_z1, c.dw_r0, c.dw_r1, c.dw_h0, c.dw_h1, c.db_z0,
-                       c.db_r0, c.db_h0, c.db_z1, c.db_r1, c.db_h1, drop_p, seed, (void*)s, nullptr, nullptr, nullptr, pre_done, next);
+                       c.db_r0, c.db_h0, c.db_z1, c.db_r1, c.db_h1, drop_p, seed, (void*)s, nullptr, nullptr, nullptr, pre_done, next,
+                       nullptr, ybuf, nodx_ok);
 }
 
 extern "C" int gh_get_forward(const gh_get_model* Mo, const gh_get_batch* Ba, float* A, float* O, gh_stream_t stream, gh_stream_t side_stream) {
@@ -587,7 +588,10 @@ extern "C" int gh_get_backward(const gh_get_model* Mo, const gh_get_batch* Ba, c
                         att_w1t16));
     GH_TRY(gh_masked_mean_bwd(Wb + w.d_q, Ba->q_ids, A + f.lens_eff, Wb + w.d_qhid, d.B, d.L, H, (void*)ss));
     GH_TRY(cell_bwd(Mo->claim, nullptr, f.q, A, Ba->q_bits, Ba->q_dinv, Ba->q_vals, nullptr, nullptr, 0, Mo->embedding, Ba->q_ids, d.B, d.L, d.D, H,
-                    Wb + w.d_qhid, Wb, w.qs, nullptr, Ba->drop_claim, Ba->seed_claim, ss));
+                    Wb + w.d_qhid, Wb, w.qs, nullptr, Ba->drop_claim, Ba->seed_claim, ss, 0, nullptr, nullptr, 0));
+    // (the claim cell keeps its da / dxp chain although no input gradient leaves it either: over B x L = 960 rows the ten weight-sized
+    //  products of the re-associated branch are as much work as the five row products they replace at h = 300 and more at h = 768,
+    //  where the configs[4] bf16 leg measured 174.3 -> 169.9 K pairs/s with this call in the branch -- DESIGN 4.20)
     // ---- second evidence cell.  (cell_bwd_impl can put the weight-gradient GEMMs on the side stream -- measured on the
     //      bench step: 6.31 -> 6.23 ms, two MFMA-bound streams mostly slow each other down, while every kernel's wall time
     //      and with it the per-kernel roofline figures inflate by 20-30 %.  Not used: one stream, honest kernel times.)
@@ -599,12 +603,15 @@ extern "C" int gh_get_backward(const gh_get_model* Mo, const gh_get_batch* Ba, c
                       Wb + w.g2, Wb, w.sc2, Wb + w.dx2, Ba->drop_gnn, Ba->seed_cell2, s, 0, nullptr));
   }
   if (phase != 1) {
+    // no input gradient leaves the first cell: cell_bwd_impl takes its re-associated branch; A_hat X goes to the
+    // second cell's `da` scratch, idle since that cell's launches were queued on this stream
+    float* const y1 = d.bf ? nullptr : Wb + w.sc2[4];
     if (fuse_gate)
       GH_TRY(cell_bwd(Mo->cell1, c16_1, f.c1, A, Ba->d_bits, Ba->d_dinv, Ba->d_vals, nullptr, goff, d.Mr, table1, ids1, d.B1, d.R, d.D, H,
-                      nullptr, Wb, w.sc1, nullptr, Ba->drop_gnn, Ba->seed_cell1, s, 1, nullptr));
+                      nullptr, Wb, w.sc1, nullptr, Ba->drop_gnn, Ba->seed_cell1, s, 1, nullptr, y1));
     else
       GH_TRY(cell_bwd(Mo->cell1, c16_1, f.c1, A, Ba->d_bits, Ba->d_dinv, Ba->d_vals, nullptr, goff, d.Mr, table1, ids1, d.B1, d.R, d.D, H,
-                      Wb + w.dx2, Wb, w.sc1, nullptr, Ba->drop_gnn, Ba->seed_cell1, s, 0, nullptr));
+                      Wb + w.dx2, Wb, w.sc1, nullptr, Ba->drop_gnn, Ba->seed_cell1, s, 0, nullptr, y1));
     GH_TRY(stream_after(s, ss, ev.ev[5]));
   }
   return 0;
