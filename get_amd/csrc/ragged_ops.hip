@@ -297,10 +297,14 @@ extern "C" int gh_evd_assemble_bwd(const float* g, const int32_t* offsets, const
   hipStream_t s = (hipStream_t)stream;
   const size_t lds_bytes = (size_t)((n_slots + 1) & ~1) * 4 + (size_t)((n_slots + 63) / 64) * 8;
   if (lds_bytes > 48 * 1024) {
+    // The kernel's static LDS (its `earlier` flag) counts against the 160 KB of a CU as well: asking for all 160 KB as DYNAMIC
+    // memory was refused, and the refusal -- ignored here -- came back as the "invalid argument" of the launch check below, on the
+    // first call above 48 KB (tests/test_gpu_ragged_paths.py, 12 600 slots).  38 000 slots need 156 752 B.
+    constexpr int max_dynamic = 160 * 1024 - 64;
     static bool attr = false;
     if (!attr) {
-      (void)hipFuncSetAttribute((const void*)evd_assemble_bwd_kernel<int64_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute((const void*)evd_assemble_bwd_kernel<int32_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      GH_CHECK_HIP(hipFuncSetAttribute((const void*)evd_assemble_bwd_kernel<int64_t>, hipFuncAttributeMaxDynamicSharedMemorySize, max_dynamic));
+      GH_CHECK_HIP(hipFuncSetAttribute((const void*)evd_assemble_bwd_kernel<int32_t>, hipFuncAttributeMaxDynamicSharedMemorySize, max_dynamic));
       attr = true;
     }
   }

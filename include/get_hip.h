@@ -241,7 +241,9 @@ int gh_concat_att_fwd(const float* left, const float* right, const float* mask, 
  * Scratch: de [b*l][heads], dpre [b*l][ha], du [b][ha].
  * Out: dleft [b][xl] (NULL ok), dright [b][l][dr]; ACCUMULATED: dw1 [ha][xl+dr], dw2 [heads][ha].
  * Two-phase use (e.g. the weight gradient of linear1 on another stream): dw1 == NULL leaves its launches out;
- * dright == NULL is the complementary call that computes ONLY dw1 from the dpre / du a first call has filled. */
+ * dright == NULL is the complementary call that computes ONLY dw1 from the dpre / du a first call has filled.
+ * ha must be a multiple of 4 and at most 1024 (the pass through the tanh layer walks float4 columns, at most 256 per row): the
+ * forward also accepts ha % 4 != 0 up to 320 and wider multiples of 4, the backward refuses both ("att_dpre: attention hidden ..."). */
 int gh_concat_att_bwd(const float* left, const float* right, const int32_t* goff, int m_real, int b, int l, int xl,
                       int dr, int ha, int heads,
                       const float* w1t, const float* w2, const float* t, const float* weights,

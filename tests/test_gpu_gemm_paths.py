@@ -34,118 +34,16 @@ from types import SimpleNamespace
 import pytest
 import torch
 
-from tests.util import _rel, _same
+from tests.util import DEV, _WS_MODE, _Fenced, _ops, _poison, _rel, _same, _workspace, _ws_written
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0") if torch.cuda.is_available() else None
-NAN = float("nan")
-FENCE = 64                       # floats of NaN on either side of every operand, at the least
 BLOCK = 320                      # columns per problem of a launch (Batch::bn)
 MAX_PROBLEMS = 12                # problems per launch (GH_MAX_PROBLEMS)
 # dW labels: tn = fast kernel, one K chunk, one atomic add per element onto dw; atomic = fast kernel, several chunks added
 # with atomics (no or too small a workspace); ws = partial tiles in the workspace, reduce_partials_kernel
 FAMILY = {"nt": "gemm NT", "split": "gemm NT split-K", "generic": "gemm generic", "ws": "gemm TN via workspace",
           "atomic": "gemm TN atomic", "tn": "gemm TN single chunk", "colsum": "column sums", "tiny": "tiny linear"}
-
-
-def _ops():
-    from get_amd import _lib, ops
-    _lib.ensure_workspace(DEV)
-    return _lib, ops
-
-
-# ----------------------------------------------------------------------------- fenced operands, poisoned workspace
-class _Fenced:
-    """Tensors placed inside NaN-filled allocations of their own; check() asserts that every fence is still all NaN."""
-
-    def __init__(self):
-        self.items = []
-
-    def put(self, name, src=None, shape=None, mis=False, dtype=torch.float32):
-        """A contiguous device tensor of `shape` (default: src's) holding `src` (None: NaN) with >= FENCE floats of NaN
-        before and after it, 16-byte aligned (mis: 4 bytes past a 16-byte boundary)."""
-        shape = tuple(src.shape if shape is None else shape)
-        n = math.prod(shape)
-        es = torch.empty((), dtype=dtype).element_size()
-        pad = FENCE * 4 // es
-        buf = torch.full((n + 2 * pad + 16,), NAN, device=DEV, dtype=dtype)
-        off = pad
-        while (buf.data_ptr() + off * es) % 16 != (4 if mis else 0):
-            off += 1
-        v = buf[off:off + n].view(shape)
-        if src is not None:
-            v.copy_(src.to(dtype))
-        assert v.is_contiguous() and v.data_ptr() % 16 == (4 if mis else 0)
-        assert off * es >= FENCE * 4 and (buf.numel() - off - n) * es >= FENCE * 4
-        self.items.append((name, buf, off, n))
-        return v
-
-    def check(self, what):
-        for name, buf, off, n in self.items:
-            ok = torch.isnan(buf[:off]).all() & torch.isnan(buf[off + n:]).all()
-            assert bool(ok), f"{what}: the NaN fence around {name} was written"
-
-
-_SMALL_WS = []                   # the 1 MiB workspace while a small-workspace case runs
-
-
-def _poison():
-    """NaN into every float of the registered workspace: split-K partial tiles and the column-sum tail."""
-    _lib, _ = _ops()
-    _lib.ensure_workspace(DEV).fill_(NAN)
-    for t in _SMALL_WS:
-        t.fill_(NAN)
-
-
-_WS_MODE = ["default"]           # default | none | small: what is registered for the stream right now
-
-
-def _ws_written():
-    """(partial tiles written, column-sum partials written) since _poison().  make_workspace (csrc/gemm_ops.hip) gives the
-    last 1/16 of the buffer, 16-byte aligned, to the column sums and the rest to the tiles, both filled from their start.
-    Without a workspace, or with the small one, the default buffer must not have been touched at all.
-    (Probing the first float of either area relies on today's layout: Batch::flush, nt_split_plan and launch_colsum3
-    each hand out their area from its start, so problem 0's chunk 0 / row block 0 lands there.  A plan that starts
-    elsewhere needs another probe.)"""
-    _lib, _ = _ops()
-    default = _lib.ensure_workspace(DEV)
-    if _WS_MODE[0] != "default":
-        assert bool(torch.isnan(default).all()), "the default workspace was written while it was not registered"
-    if _WS_MODE[0] == "none":
-        return False, False
-    ws = default if _WS_MODE[0] == "default" else _SMALL_WS[0]
-    nbytes = ws.numel() * 4
-    cs = ((nbytes - ((nbytes // 16) & ~15)) & ~15) // 4
-    return not bool(torch.isnan(ws[0])), not bool(torch.isnan(ws[cs]))
-
-
-class _workspace:
-    """with _workspace(None): no workspace for the current stream; _workspace(1): a 1 MiB one.  The default workspace
-    is registered again on the way out."""
-
-    def __init__(self, mib):
-        self.mib = mib
-
-    def __enter__(self):
-        _lib, _ = _ops()
-        if self.mib is None:
-            _lib.call("gh_set_stream_workspace", _lib.stream(), None, 0)
-            _WS_MODE[0] = "none"
-        else:
-            small = torch.empty(self.mib << 18, device=DEV, dtype=torch.float32)
-            _SMALL_WS.append(small)
-            _lib.call("gh_set_stream_workspace", _lib.stream(), small.data_ptr(), small.numel() * 4)
-            _WS_MODE[0] = "small"
-
-    def __exit__(self, *exc):
-        from get_amd import _lib
-        torch.cuda.synchronize()
-        _WS_MODE[0] = "default"
-        _SMALL_WS.clear()
-        _lib._workspaces.clear()          # the next ensure_workspace registers a default-sized buffer again
-        _lib.ensure_workspace(DEV)
-        return False
 
 
 # ----------------------------------------------------------------------------- inputs and the float64 reference

@@ -9,60 +9,15 @@ from get_amd.synth import make_embeddings, make_raw_batch, make_state_dict
 from oracle import get_oracle as O
 from oracle.assemble import assemble_inputs, reference_kargs
 from oracle.cases_model import MODEL_CASES
-from tests.util import check_grad, load
+from tests.util import build_model, check_grad, composite_vs_modules, load, run_model, to_dev  # noqa: F401 (build_model, to_dev: imported from here by other test files)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-def build_model(cfg, seed):
-    from get_amd import modules
-    emb, art, clm = make_embeddings(cfg, seed)
-    model = modules.Graph_basedSemantiStructure(cfg.model_params(emb, art, clm))
-    full = model.state_dict()
-    full.update({k: torch.from_numpy(v) for k, v in make_state_dict(cfg, seed).items()})
-    model.load_state_dict(full, strict=True)
-    return model.to(DEV).train(False)
-
-
-def to_dev(kargs):
-    out = {}
-    for k, v in kargs.items():
-        if torch.is_tensor(v):
-            out[k] = v.to(DEV)
-        elif isinstance(v, tuple):
-            out[k] = tuple(t.to(DEV) if torch.is_tensor(t) else t for t in v)
-        else:
-            out[k] = v
-    return out
-
-
 def run_case(name, native_graphs=False, int32_inputs=False):
     cfg, seed = MODEL_CASES[name]
-    model = build_model(cfg, seed)
-    raw = make_raw_batch(cfg, seed)
-    inp = assemble_inputs(raw, cfg, O.convert_text)
-    kargs = to_dev(reference_kargs(inp, torch, output_ranking=True))
-    query = torch.from_numpy(inp["query"]).to(DEV)
-    document = torch.from_numpy(inp["document"]).to(DEV)
-    if native_graphs:
-        from get_amd import ops
-        qa, q_ids, q_n = ops.graph_build(torch.from_numpy(raw["claim_tokens"]).to(DEV),
-                                         torch.from_numpy(raw["claim_len"]).to(DEV), cfg.window)
-        da, d_ids, d_n = ops.graph_build(torch.from_numpy(raw["evd_tokens"]).to(DEV),
-                                         torch.from_numpy(raw["evd_len"]).to(DEV), cfg.window)
-        assert np.array_equal(q_ids.cpu().numpy(), inp["query"]) and np.array_equal(d_ids.cpu().numpy(), inp["doc_ids"])
-        assert np.array_equal(q_n.cpu().numpy(), inp["query_lens"])
-        if native_graphs == "compact":     # node-compact fast path (ops.RaggedPlan): padding nodes skipped where inert
-            da = da.with_plan(ops.RaggedPlan(d_n, d_ids, int(inp["doc_lens"].sum()) if "doc_lens" in inp else int(d_n.sum().item())))
-        kargs["query_adj"], kargs["docs_adj"] = qa, da
-    if int32_inputs:       # the evaluation path hands int32 ids/lens (char_man_fitter_query_repr1.py:298-316)
-        query, document = query.int(), document.int()
-        for k in ("query_lens", "doc_content_without_padding_evidences", "doc_sources", "query_sources"):
-            kargs[k] = kargs[k].int()
-    phi, (ww, ew) = model(query, document, **kargs)
-    loss = torch.nn.functional.cross_entropy(phi, torch.from_numpy(inp["labels"]).to(DEV))
-    return cfg, model, inp, phi, ww, ew, loss
+    return run_model(cfg, seed, native_graphs=native_graphs, int32_inputs=int32_inputs)
 
 
 @pytest.mark.parametrize("name", list(MODEL_CASES))
@@ -989,25 +944,8 @@ def test_composite_entry_points_equal_the_module_by_module_path(name, native, mo
     module-by-module path on the same inputs: same kernels underneath, so logits, attention weights, scores, keep-sets
     and every gradient agree to fp32 summation-order noise (the composite sums the claim vector's gradient in a different
     order and projects the word attention's left input once per claim instead of once per pair)."""
-    from get_amd import fused
-    res = {}
-    for on in (False, True):
-        monkeypatch.setattr(fused, "ENABLED", on)
-        cfg, model, inp, phi, ww, ew, loss = run_case(name, native_graphs=native)
-        assert (getattr(model, "_gh_binding", None) is not None) == on, "the wrong path ran"
-        loss.backward()
-        torch.cuda.synchronize()
-        res[on] = dict(phi=phi.detach().clone(), ww=ww.detach().clone(), ew=ew.detach().clone(),
-                       score=model.ggnn_with_gsl.last_score.clone(), keep=model.ggnn_with_gsl.last_keep.clone(),
-                       grads={k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None})
-    a, b = res[False], res[True]
-    assert torch.equal(a["keep"], b["keep"])
-    for k in ("phi", "ww", "ew", "score"):
-        assert float((a[k] - b[k]).abs().max()) <= 2e-6 * max(1.0, float(a[k].abs().max())), k
-    assert set(a["grads"]) == set(b["grads"])
-    for k, g in a["grads"].items():
-        scale = max(float(g.abs().max()), 1e-8)
-        assert float((g - b["grads"][k]).abs().max()) <= 2e-5 * scale, k
+    cfg, seed = MODEL_CASES[name]
+    composite_vs_modules(cfg, seed, native)
 
 
 def test_composite_path_with_flat_trainer_matches_autograd_gradients():

@@ -938,3 +938,9 @@ def test_evd_assemble_bwd_writes_every_row_of_d_avg():
             want = g[c, j, :xa] if j < n_max else np.zeros(xa, np.float32)
             assert np.array_equal(got[lo + j], want), (c, j)
         lo += int(n)
+    # d_table directly: the float64 scatter-add over the REAL slots (padding slots carry gradient here and must not join);
+    # every slot count, id type and the LDS opt-in: tests/test_gpu_ragged_paths.py
+    from tests.util import TOL, r_evd_assemble_bwd, rel_close
+    want_avg, want_table = r_evd_assemble_bwd(g, seg.offsets.cpu().numpy(), src, 6, xa, np.zeros((6, ds)))
+    assert np.array_equal(got, want_avg)
+    rel_close(d_table, want_table, TOL, "evd_assemble_bwd d_table", fam="ragged")

@@ -1,5 +1,6 @@
 """Shared helpers for the parity tests (fixtures, gradient summaries, tolerances)."""
 import json
+import math
 import os
 import subprocess
 import sys
@@ -116,6 +117,111 @@ def _same(a, b, what):
     for i, (u, v) in enumerate(zip(a, b)):
         if u is not None:
             bits_equal(u, v, f"{what}: output {i} of two calls")
+
+
+# ----------------------------------------------------------------------------- fenced operands, poisoned workspace
+# (shared by the direct-ABI path tests: tests/test_gpu_gemm_paths.py, test_gpu_concat_att_paths.py, test_gpu_ragged_paths.py)
+DEV = torch.device("cuda:0") if torch.cuda.is_available() else None
+NAN = float("nan")
+FENCE = 64                       # floats of NaN on either side of every operand, at the least
+
+
+def _ops():
+    from get_amd import _lib, ops
+    _lib.ensure_workspace(DEV)
+    return _lib, ops
+
+
+class _Fenced:
+    """Tensors placed inside NaN-filled allocations of their own; check() asserts that every fence is still all NaN."""
+
+    def __init__(self):
+        self.items = []
+
+    def put(self, name, src=None, shape=None, mis=False, dtype=torch.float32):
+        """A contiguous device tensor of `shape` (default: src's) holding `src` (None: NaN) with >= FENCE floats of NaN
+        before and after it, 16-byte aligned (mis: 4 bytes past a 16-byte boundary)."""
+        shape = tuple(src.shape if shape is None else shape)
+        n = math.prod(shape)
+        es = torch.empty((), dtype=dtype).element_size()
+        pad = FENCE * 4 // es
+        buf = torch.full((n + 2 * pad + 16,), NAN, device=DEV, dtype=dtype)
+        off = pad
+        while (buf.data_ptr() + off * es) % 16 != (4 if mis else 0):
+            off += 1
+        v = buf[off:off + n].view(shape)
+        if src is not None:
+            v.copy_(src.to(dtype))
+        assert v.is_contiguous() and v.data_ptr() % 16 == (4 if mis else 0)
+        assert off * es >= FENCE * 4 and (buf.numel() - off - n) * es >= FENCE * 4
+        self.items.append((name, buf, off, n))
+        return v
+
+    def check(self, what):
+        for name, buf, off, n in self.items:
+            ok = torch.isnan(buf[:off]).all() & torch.isnan(buf[off + n:]).all()
+            assert bool(ok), f"{what}: the NaN fence around {name} was written"
+
+
+_SMALL_WS = []                   # the 1 MiB workspace while a small-workspace case runs
+
+
+def _poison():
+    """NaN into every float of the registered workspace: split-K partial tiles and the column-sum tail."""
+    _lib, _ = _ops()
+    _lib.ensure_workspace(DEV).fill_(NAN)
+    for t in _SMALL_WS:
+        t.fill_(NAN)
+
+
+_WS_MODE = ["default"]           # default | none | small: what is registered for the stream right now
+
+
+def _ws_written():
+    """(partial tiles written, column-sum partials written) since _poison().  make_workspace (csrc/gemm_ops.hip) gives the
+    last 1/16 of the buffer, 16-byte aligned, to the column sums and the rest to the tiles, both filled from their start.
+    Without a workspace, or with the small one, the default buffer must not have been touched at all.
+    (Probing the first float of either area relies on today's layout: Batch::flush, nt_split_plan and launch_colsum3
+    each hand out their area from its start, so problem 0's chunk 0 / row block 0 lands there.  A plan that starts
+    elsewhere needs another probe.)"""
+    _lib, _ = _ops()
+    default = _lib.ensure_workspace(DEV)
+    if _WS_MODE[0] != "default":
+        assert bool(torch.isnan(default).all()), "the default workspace was written while it was not registered"
+    if _WS_MODE[0] == "none":
+        return False, False
+    ws = default if _WS_MODE[0] == "default" else _SMALL_WS[0]
+    nbytes = ws.numel() * 4
+    cs = ((nbytes - ((nbytes // 16) & ~15)) & ~15) // 4
+    return not bool(torch.isnan(ws[0])), not bool(torch.isnan(ws[cs]))
+
+
+class _workspace:
+    """with _workspace(None): no workspace for the current stream; _workspace(1): a 1 MiB one.  The default workspace
+    is registered again on the way out."""
+
+    def __init__(self, mib):
+        self.mib = mib
+
+    def __enter__(self):
+        _lib, _ = _ops()
+        if self.mib is None:
+            _lib.call("gh_set_stream_workspace", _lib.stream(), None, 0)
+            _WS_MODE[0] = "none"
+        else:
+            small = torch.empty(self.mib << 18, device=DEV, dtype=torch.float32)
+            _SMALL_WS.append(small)
+            _lib.call("gh_set_stream_workspace", _lib.stream(), small.data_ptr(), small.numel() * 4)
+            _WS_MODE[0] = "small"
+
+    def __exit__(self, *exc):
+        from get_amd import _lib
+        torch.cuda.synchronize()
+        _WS_MODE[0] = "default"
+        _SMALL_WS.clear()
+        _lib._workspaces.clear()          # the next ensure_workspace registers a default-sized buffer again
+        _lib.ensure_workspace(DEV)
+        return False
 
 
 # ----------------------------------------------------------------------------- golden fixtures
@@ -375,3 +481,233 @@ def g_depad(counts, n_max, r, ids, adj):
                               (i_.astype(np.int32), nn, pat, dinv, a32, bad, weighted)):
                 out[key].append(v)
     return out
+
+
+# ----------------------------------------------------------------------------- concat attention restatement (float64, tests only)
+# What gh_concat_att_fwd computes and saves, as plain torch ops; the reference of tests/test_gpu_concat_att_paths.py, checked
+# on its own against the oracle and the reference's goldens by tests/test_concat_restatement_cpu.py.
+def _concat64(left, right, mask, w1, w2):
+    """left (b, xl) or None, right (b, l, dr), mask (b, l) with 0 = padded, w1 (ha, xl + dr), w2 (heads, ha) ->
+    u (b, ha), t (b, l, ha), e (b, l, heads), weights (b, l, heads), attended (b, dr, heads).  A pair whose rows are all
+    masked has NaN weights and NaN attended, as the softmax of an all -inf column has."""
+    xl = 0 if left is None else left.shape[1]
+    u = left @ w1[:, :xl].t() if left is not None else right.new_zeros((right.shape[0], w1.shape[0]))
+    t = torch.tanh(right @ w1[:, xl:].t() + u.unsqueeze(1))
+    e = t @ w2.t()
+    w = torch.softmax(e.masked_fill((mask == 0).unsqueeze(-1), float("-inf")), dim=1)
+    attended = torch.einsum("bld,blc->bdc", right, w)
+    return u, t, e, w, attended
+
+
+# ----------------------------------------------------------------------------- ragged restatements (numpy, tests only)
+# Plain statements of what csrc/ragged_ops.hip computes: the references of tests/test_gpu_ragged_paths.py, checked against the
+# oracle's pad_left / pad_right by tests/test_concat_restatement_cpu.py.
+def r_seg_offsets(counts, b1):
+    """offsets int32 (b + 1,), pair2claim int32 (b1,), has float32 (b,): pairs beyond sum(counts) map to claim 0, pairs
+    beyond b1 do not exist."""
+    counts = np.asarray(counts, dtype=np.int64)
+    offsets = np.zeros(len(counts) + 1, np.int32)
+    offsets[1:] = np.cumsum(counts)
+    p2c = np.zeros(b1, np.int32)
+    full = np.repeat(np.arange(len(counts), dtype=np.int32), counts)
+    n = min(b1, len(full))
+    p2c[:n] = full[:n]
+    return offsets, p2c, (counts > 0).astype(np.float32)
+
+
+def r_seg_sum(src, offsets):
+    """float64 (b, x): the sum of rows [offsets[c], offsets[c + 1]) of src, exact zeros for an empty claim."""
+    src = np.asarray(src, dtype=np.float64)
+    out = np.zeros((len(offsets) - 1, src.shape[1]), np.float64)
+    for c in range(len(offsets) - 1):
+        out[c] = src[offsets[c]:offsets[c + 1]].sum(0)
+    return out
+
+
+def r_seg_pad(src, offsets, n_max):
+    """(b, n_max, x): the first min(count, n_max) rows of every claim, zeros behind them."""
+    src = np.asarray(src)
+    out = np.zeros((len(offsets) - 1, n_max, src.shape[1]), src.dtype)
+    for c in range(len(offsets) - 1):
+        k = min(int(offsets[c + 1] - offsets[c]), n_max)
+        out[c, :k] = src[offsets[c]:offsets[c] + k]
+    return out
+
+
+def r_seg_unpad(padded, offsets, dst0):
+    """dst0 (b1, x) with rows offsets[c] + j, j < min(count, n_max), replaced by padded[c][j]; the other rows untouched."""
+    padded = np.asarray(padded)
+    out = np.array(dst0, copy=True)
+    for c in range(len(offsets) - 1):
+        k = min(int(offsets[c + 1] - offsets[c]), padded.shape[1])
+        out[offsets[c]:offsets[c] + k] = padded[c, :k]
+    return out
+
+
+def r_masked_mean(hid, ids, lens):
+    """float64 (b, h): sum over the tokens with id > 0 of hid, divided by lens."""
+    hid = np.asarray(hid, dtype=np.float64)
+    live = (np.asarray(ids) > 0).astype(np.float64)
+    return (hid * live[:, :, None]).sum(1) / np.asarray(lens, dtype=np.float64)[:, None]
+
+
+def r_masked_mean_bwd(g, ids, lens):
+    """float64 (b, l, h): g / lens on the rows of tokens with id > 0, exact zeros elsewhere."""
+    g = np.asarray(g, dtype=np.float64)
+    live = (np.asarray(ids) > 0).astype(np.float64)
+    return live[:, :, None] * (g / np.asarray(lens, dtype=np.float64)[:, None])[:, None, :]
+
+
+def r_clamp_sources(sources, table_rows):
+    """(row of the table every slot reads, number of ids the kernel counts as clamped): -1 is the padding id (row 0, not
+    counted), every other id outside [0, table_rows) goes to the nearest row and is counted once."""
+    s = np.asarray(sources, dtype=np.int64)
+    return np.clip(s, 0, table_rows - 1), int(((s < -1) | (s >= table_rows)).sum())
+
+
+def r_evd_assemble(avg, offsets, table, sources, document, n_max):
+    """right (b, n_max, xa + ds) and mask (b, n_max) float32, and the clamped-id count; table None: ds = 0."""
+    avg = np.asarray(avg, dtype=np.float32)
+    right = r_seg_pad(avg, offsets, n_max)
+    clamped = 0
+    if table is not None:
+        rows, clamped = r_clamp_sources(sources, table.shape[0])
+        right = np.concatenate([right, np.asarray(table, dtype=np.float32)[rows]], axis=-1)
+    mask = (np.asarray(document, dtype=np.int64).sum(-1) >= 1).astype(np.float32)
+    return right, mask, clamped
+
+
+def r_evd_assemble_bwd(g, offsets, sources, table_rows, xa, d_table0):
+    """d_avg float32 (b1, xa): the slot rows of g[:, :, :xa], zeros for a claim's pairs beyond n_max; d_table float64 =
+    d_table0 + the scatter-add of g[:, :, xa:] over the REAL slots (slot < min(count, n_max)) by clamped source id."""
+    g = np.asarray(g)
+    b, n_max = g.shape[:2]
+    d_avg = np.zeros((int(offsets[-1]), xa), np.float32)
+    d_table = None if d_table0 is None else np.array(d_table0, dtype=np.float64)
+    rows = r_clamp_sources(sources, table_rows)[0] if d_table is not None else None
+    for c in range(b):
+        k = min(int(offsets[c + 1] - offsets[c]), n_max)
+        d_avg[offsets[c]:offsets[c] + k] = g[c, :k, :xa]
+        for j in range(k if d_table is not None else 0):
+            d_table[rows[c, j]] += g[c, j, xa:].astype(np.float64)
+    return d_avg, d_table
+
+
+# ----------------------------------------------------------------------------- the whole model (GPU tests)
+def build_model(cfg, seed):
+    from get_amd import modules
+    from get_amd.synth import make_embeddings, make_state_dict
+    emb, art, clm = make_embeddings(cfg, seed)
+    model = modules.Graph_basedSemantiStructure(cfg.model_params(emb, art, clm))
+    full = model.state_dict()
+    full.update({k: torch.from_numpy(v) for k, v in make_state_dict(cfg, seed).items()})
+    model.load_state_dict(full, strict=True)
+    return model.to(DEV).train(False)
+
+
+def to_dev(kargs):
+    out = {}
+    for k, v in kargs.items():
+        if torch.is_tensor(v):
+            out[k] = v.to(DEV)
+        elif isinstance(v, tuple):
+            out[k] = tuple(t.to(DEV) if torch.is_tensor(t) else t for t in v)
+        else:
+            out[k] = v
+    return out
+
+
+def run_model(cfg, seed, native_graphs=False, int32_inputs=False):
+    """One forward of the drop-in model on the synthetic batch of (cfg, seed): reference-API inputs, graphs built on the
+    device (native_graphs) or the node-compact plan on top (native_graphs == "compact")."""
+    from get_amd.synth import make_raw_batch
+    from oracle import get_oracle as O
+    from oracle.assemble import assemble_inputs, reference_kargs
+    model = build_model(cfg, seed)
+    raw = make_raw_batch(cfg, seed)
+    inp = assemble_inputs(raw, cfg, O.convert_text)
+    kargs = to_dev(reference_kargs(inp, torch, output_ranking=True))
+    query = torch.from_numpy(inp["query"]).to(DEV)
+    document = torch.from_numpy(inp["document"]).to(DEV)
+    if native_graphs:
+        from get_amd import ops
+        qa, q_ids, q_n = ops.graph_build(torch.from_numpy(raw["claim_tokens"]).to(DEV),
+                                         torch.from_numpy(raw["claim_len"]).to(DEV), cfg.window)
+        da, d_ids, d_n = ops.graph_build(torch.from_numpy(raw["evd_tokens"]).to(DEV),
+                                         torch.from_numpy(raw["evd_len"]).to(DEV), cfg.window)
+        assert np.array_equal(q_ids.cpu().numpy(), inp["query"]) and np.array_equal(d_ids.cpu().numpy(), inp["doc_ids"])
+        assert np.array_equal(q_n.cpu().numpy(), inp["query_lens"])
+        if native_graphs == "compact":     # node-compact fast path (ops.RaggedPlan): padding nodes skipped where inert
+            da = da.with_plan(ops.RaggedPlan(d_n, d_ids, int(inp["doc_lens"].sum()) if "doc_lens" in inp else int(d_n.sum().item())))
+        kargs["query_adj"], kargs["docs_adj"] = qa, da
+    if int32_inputs:       # the evaluation path hands int32 ids/lens (char_man_fitter_query_repr1.py:298-316)
+        query, document = query.int(), document.int()
+        for k in ("query_lens", "doc_content_without_padding_evidences", "doc_sources", "query_sources"):
+            kargs[k] = kargs[k].int()
+    phi, (ww, ew) = model(query, document, **kargs)
+    loss = torch.nn.functional.cross_entropy(phi, torch.from_numpy(inp["labels"]).to(DEV))
+    return cfg, model, inp, phi, ww, ew, loss
+
+
+def composite_vs_modules(cfg, seed, native, oracle=False):
+    """get_amd/fused.py (gh_get_forward / gh_get_backward: the whole model in one library call each) against the
+    module-by-module path on the same inputs: equal keep-sets, logits / weights / scores within 2e-6 max(1, scale), every
+    gradient within 2e-5 of its scale.  oracle: the composite run also against oracle.get_oracle.model_forward at the model
+    tests' bounds (logits 1e-4, weights 1e-5, gradients 1e-3 of their scale + 1e-5)."""
+    from get_amd import fused
+    res = {}
+    was = fused.ENABLED
+    try:
+        for on in (False, True):
+            fused.ENABLED = on
+            cfg, model, inp, phi, ww, ew, loss = run_model(cfg, seed, native_graphs=native)
+            assert (getattr(model, "_gh_binding", None) is not None) == on, "the wrong path ran"
+            loss.backward()
+            torch.cuda.synchronize()
+            res[on] = dict(phi=phi.detach().clone(), ww=ww.detach().clone(), ew=ew.detach().clone(),
+                           score=model.ggnn_with_gsl.last_score.clone(), keep=model.ggnn_with_gsl.last_keep.clone(),
+                           grads={k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None})
+    finally:
+        fused.ENABLED = was
+    a, b = res[False], res[True]
+    assert torch.equal(a["keep"], b["keep"])
+    for k in ("phi", "ww", "ew", "score"):
+        scale = max(1.0, float(a[k].abs().max()))
+        err = float((a[k] - b[k]).abs().max())
+        WORST["composite-vs-module"] = max(WORST.get("composite-vs-module", 0.0), err / scale)
+        assert err <= 2e-6 * scale, k
+    assert set(a["grads"]) == set(b["grads"])
+    for k, g in a["grads"].items():
+        scale = max(float(g.abs().max()), 1e-8)
+        err = float((g - b["grads"][k]).abs().max())
+        WORST["composite-vs-module"] = max(WORST.get("composite-vs-module", 0.0), err / scale)
+        assert err <= 2e-5 * scale, k
+    print(f"composite vs modules (seed {seed}, native={native}): worst err / scale so far {WORST['composite-vs-module']:.3e}")
+    if oracle:
+        _model_vs_oracle(cfg, seed, inp, b)
+    return res
+
+
+def _model_vs_oracle(cfg, seed, inp, got):
+    from get_amd.synth import make_embeddings, make_state_dict
+    from oracle import get_oracle as O
+    T = lambda x: torch.from_numpy(np.ascontiguousarray(x))
+    emb, art, _ = make_embeddings(cfg, seed)
+    p = {k: T(v).requires_grad_(True) for k, v in make_state_dict(cfg, seed).items()}
+    p["embedding.weight"], p["article_source_embs.weight"] = T(emb), T(art)
+    phi, ww, ew = O.model_forward(p, cfg.__dict__, T(inp["query"]), T(inp["document"]), T(inp["query_adj"]), T(inp["doc_ids"]),
+                                  T(inp["doc_adj"]), T(inp["query_lens"]), inp["evd_counts"], T(inp["doc_sources"]),
+                                  T(inp["query_sources"]))
+    O.cross_entropy(phi, T(inp["labels"])).backward()
+    assert float((got["phi"].cpu() - phi.detach()).abs().max()) <= 1e-4, "logits against the oracle"
+    assert float((got["ww"].cpu() - ww.detach()).abs().max()) <= 1e-5, "word weights against the oracle"
+    assert float((got["ew"].cpu() - ew.detach()).abs().max()) <= 1e-5, "evidence weights against the oracle"
+    n = 0
+    for k, g in got["grads"].items():
+        if k in p and p[k].grad is not None:
+            want = p[k].grad.double()
+            scale = max(float(want.abs().max()), 1e-6)
+            err = float((g.double().cpu() - want).abs().max())
+            assert err <= 1e-5 + 1e-3 * scale, f"{k} against the oracle: {err:.3e} vs scale {scale:.3e}"
+            n += 1
+    assert n >= 10, n
