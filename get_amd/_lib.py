@@ -19,6 +19,7 @@ _I = ctypes.c_int
 _F = ctypes.c_float
 _L = ctypes.c_int64
 _U = ctypes.c_uint32
+_D = ctypes.c_double
 ABI_VERSION = 10         # GH_ABI_VERSION of include/get_hip.h
 
 # name -> argtypes (mirrors include/get_hip.h; tests/test_abi.py checks the two agree)
@@ -106,6 +107,11 @@ SIGNATURES = {
     "gh_get_prepare": [_P, _P, _I, _I, _P, _P, _I, _I, _I] + [_P] * 8 + [_I] + [_P] * 5 + [_P, _P, _P],
     "gh_get_struct_sizes": [_P],
     "gh_cls_metrics": [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P],
+    "gh_rank_metrics": [_P, _I, _P, _P, _P, _I, _I, _D, _P, _I, _P, _P, _P, _P, _P],
+    "gh_rank_hinge_fwd": [_P, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P],
+    "gh_rank_hinge_bwd": [_P, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P],
+    "gh_rank_ce_fwd": [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P],
+    "gh_rank_ce_bwd": [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P],
     # library-owned RCCL communicator (csrc/comm_ops.hip; librccl is dlopen'ed on first use)
     "gh_comm_unique_id": [_P],
     "gh_comm_init": [_P, _I, _I, _P],

@@ -44,4 +44,17 @@ def install():
     _module("matchzoo.modules", Attention=M.Attention, BidirectionalAttention=M.BidirectionalAttention,
             MatchModule=M.MatchModule, RNNDropout=M.RNNDropout, StackedBRNN=M.StackedBRNN, GaussianKernel=M.GaussianKernel,
             Matching=M.Matching, torch=torch, nn=nn)
+    # what those baselines train against and are scored with.  The base fitter imports the metric SUBMODULES
+    # (Fitting/densebaseline_fit.py:19-20), so every file of matchzoo/metrics and matchzoo/losses is served under its own name
+    from . import ranking as R
+    by_file = {"precision": R.Precision, "average_precision": R.AveragePrecision,
+               "mean_average_precision": R.MeanAveragePrecision, "mean_reciprocal_rank": R.MeanReciprocalRank,
+               "discounted_cumulative_gain": R.DiscountedCumulativeGain,
+               "normalized_discounted_cumulative_gain": R.NormalizedDiscountedCumulativeGain}
+    subs = {name: _module("matchzoo.metrics." + name, BaseMetric=R.BaseMetric, np=np, **{cls.__name__: cls})
+            for name, cls in by_file.items()}
+    _module("matchzoo.metrics", **subs, **{cls.__name__: cls for cls in by_file.values()})
+    losses = {"rank_hinge_loss": M.RankHingeLoss, "rank_cross_entropy_loss": M.RankCrossEntropyLoss}
+    subs = {name: _module("matchzoo.losses." + name, torch=torch, nn=nn, **{cls.__name__: cls}) for name, cls in losses.items()}
+    _module("matchzoo.losses", **subs, **{cls.__name__: cls for cls in losses.values()})
     return M

@@ -15,6 +15,7 @@ load unchanged:
   Models/BiDAF/bidaf_model.py                  BiDAF
   matchzoo/modules                             Attention, BidirectionalAttention, MatchModule, Matching, GaussianKernel,
                                                RNNDropout, StackedBRNN
+  matchzoo/losses                              RankHingeLoss, RankCrossEntropyLoss
 
 Adjacency arguments may be the reference's dense ``(N,R,R)`` tensors (any float dtype; packed once
 on the device, values kept exactly) or a native :class:`get_amd.ops.PackedAdj` from
@@ -1236,3 +1237,63 @@ class StackedBRNN(nn.Module):
         p, seed = _encoder_drop(self.training and self.dropout_output, self.dropout_rate)
         self.last_output_seed = seed if p > 0 else None
         return ops.feat_dropout(output, p, seed).contiguous()
+
+
+# ------------------------------------------------------------------ matchzoo/losses/rank_hinge_loss.py:7-86
+class RankHingeLoss(nn.Module):
+    """forward(y_pred (B (num_neg + 1), c), y_true) -> the hinge loss max(0, margin - (pos - mean of the negatives)) of every
+    instance (its positive row and the num_neg rows behind it; ops.rank_hinge), reduced by 'none' (B, c), 'mean' or 'sum'.
+    y_true is not read, as in the reference, and may be None."""
+
+    __constants__ = ['num_neg', 'margin', 'reduction']
+
+    def __init__(self, num_neg: int = 1, margin: float = 1., reduction: str = 'mean'):
+        super().__init__()
+        self.num_neg = num_neg
+        self.margin = margin
+        self.reduction = reduction
+
+    def forward(self, y_pred, y_true=None):
+        return ops.rank_hinge(y_pred, self.num_neg, self.margin, self.reduction)
+
+    @property
+    def num_neg(self):
+        return self._num_neg
+
+    @num_neg.setter
+    def num_neg(self, value):
+        self._num_neg = value
+
+    @property
+    def margin(self):
+        return self._margin
+
+    @margin.setter
+    def margin(self, value):
+        self._margin = value
+
+
+# ------------------------------------------------------------------ matchzoo/losses/rank_cross_entropy_loss.py:7-48
+class RankCrossEntropyLoss(nn.Module):
+    """forward(y_pred, y_true (B (num_neg + 1), c)) -> -mean over the instances of sum(labels * log_softmax(logits)), logits and
+    labels being the instance's num_neg + 1 rows side by side (ops.rank_cross_entropy).
+
+    One deviation: the reference takes log(softmax(x)), which is -inf for a logit some 104 below its row maximum and NaN under
+    a zero label (logits [0, -200] with labels [1, 0] give nan); the stable log-softmax here returns the finite value."""
+
+    __constants__ = ['num_neg']
+
+    def __init__(self, num_neg: int = 1):
+        super().__init__()
+        self.num_neg = num_neg
+
+    def forward(self, y_pred, y_true):
+        return ops.rank_cross_entropy(y_pred, y_true, self.num_neg)
+
+    @property
+    def num_neg(self):
+        return self._num_neg
+
+    @num_neg.setter
+    def num_neg(self, value):
+        self._num_neg = value

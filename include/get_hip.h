@@ -772,6 +772,78 @@ int gh_get_prepare(const int32_t* claim_tokens, const int32_t* claim_len, int b,
 int gh_cls_metrics(const float* phi, int ldphi, const void* labels, int labels_i64, int n, int c, int pos_class,
                    int32_t* pred, int64_t* out, gh_stream_t stream);
 
+/* ---- ranking metrics: matchzoo/metrics/{precision, average_precision, mean_average_precision, mean_reciprocal_rank,
+ *      discounted_cumulative_gain, normalized_discounted_cumulative_gain}.py for every group of a ragged batch in ONE launch.
+ *   scores [n]      float, or double when scores_f64 (widened to double either way: equal values give equal results)
+ *   labels [n]      double
+ *   offsets [g+1]   int32 on the device, non-decreasing from 0 to n: group q is the items offsets[q] .. offsets[q+1] (the ragged
+ *                   convention of gh_seg_offsets); an empty group is legal and scores 0 everywhere
+ *   offsets_host    the same g + 1 values in HOST memory: the limits below are checked on them before anything is launched (the
+ *                   kernel also skips a group whose device offsets leave [0, n] or the group limit, writing nothing for it)
+ *   ks [nk]         int32 in HOST memory, the cut-offs k of precision@k, dcg@k and ndcg@k
+ *   An item is relevant when label > threshold.
+ *   rank [n]        0-based position of every item in the reference's ordering of its group, sorted(key=score, reverse=True)
+ *                   (engine/base_metric.py:36-39; stable: ties to the lower index): #{j : s_j > s_i} + #{j < i : s_j == s_i} with
+ *                   IEEE comparisons on values (-0.0 == 0.0, +-inf ordinary values).  A permutation of 0 .. len-1 per group.
+ *   group_int [g][3 + nk], exact:
+ *     [0] items of the group   [1] n_rel, its relevant items   [2] 1-based position of the first relevant item, 0 if none
+ *     [3 + i] hits: relevant items at positions < ks[i]
+ *   group_f64 [g][3 + 3 nk]:
+ *     [0] AveragePrecision: (1/len) sum_{k=1..len} hits0(k) / k, hits0 counted at threshold 0 whatever `threshold` is
+ *         (average_precision.py:41 builds Precision(k + 1) with the default threshold)
+ *     [1] MeanAveragePrecision: sum over the relevant positions idx of (relevant items up to idx) / (idx + 1), over n_rel; 0 if none
+ *     [2] MeanReciprocalRank: 1 / group_int[2]; 0 if none
+ *     [3 + i] Precision@ks[i] = hits / ks[i]
+ *     [3 + nk + i] DCG@ks[i] = sum over the relevant positions p < ks[i] of (2^label - 1) / ln(2 + p)
+ *     [3 + 2 nk + i] NDCG@ks[i] = DCG / IDCG, 0 if IDCG == 0; IDCG is the DCG of the group ordered by label (stable likewise)
+ *   nan_count [2]   NaN scores, NaN labels.  A NaN compares false with everything, as it does in Python's sort, whose result is
+ *                   then unspecified: when either counter is nonzero the float outputs of the groups concerned mean nothing.
+ * Every per-group float is summed by one wave in an order that depends on the group's length and k only (lane l adds the
+ * positions l, l + 64, ..., then a butterfly over the lanes): no floating-point atomics, two runs are bit-identical.  Each term
+ * is correct to a few ulp and non-negative, so a value differs from the reference's left-to-right sum by less than
+ * 1024 * 4 * 2^-53 relative; a value that is 0 in the reference is exactly 0.
+ * Limits: 1 <= g <= GH_RANK_MAX_GROUPS, 0 <= n <= GH_RANK_MAX_ITEMS, 1 <= nk <= GH_RANK_MAX_KS, every ks[i] >= 1, a finite or
+ * infinite (not NaN) threshold, offsets_host[0] == 0, offsets_host[g] == n, non-decreasing, at most GH_RANK_MAX_GROUP items per
+ * group (the four 8 KB LDS tiles of a workgroup).  A call that breaks one returns an error and nothing is written. */
+#define GH_RANK_MAX_GROUP 1024
+#define GH_RANK_MAX_KS 8
+#define GH_RANK_MAX_GROUPS (1 << 24)
+#define GH_RANK_MAX_ITEMS (1 << 30)
+int gh_rank_metrics(const void* scores, int scores_f64, const double* labels, const int32_t* offsets, const int32_t* offsets_host,
+                    int n, int g, double threshold, const int32_t* ks, int nk, int32_t* rank, int32_t* group_int, double* group_f64,
+                    int32_t* nan_count, gh_stream_t stream);
+
+/* ---- ranking losses on y [rows] rows of c floats, ld >= c floats apart: instance b is row b (num_neg + 1), its positive, and the
+ *      num_neg rows behind it, its negatives.  fp32; every value is summed in a fixed order (two runs are bit-identical) and
+ *      every gradient element has one writer.  dy is [rows][c], contiguous.
+ * Limits (all four): 1 <= c <= ld, 1 <= rows <= GH_RANK_MAX_ROWS and rows a multiple of num_neg + 1 (the reference raises a
+ * shape error otherwise), num_neg <= GH_RANK_MAX_NEG, num_neg >= 1 for the hinge loss and >= 0 for the cross-entropy.  A call
+ * that breaks one returns an error and nothing is written.
+ *
+ * RankHingeLoss (matchzoo/losses/rank_hinge_loss.py:54-66), B = rows / (num_neg + 1):
+ *   neg_mean [B] (saved for the backward) = mean of the instance's num_neg * c negative entries
+ *   element (b, j) = max(0, margin - (y_pos[b][j] - neg_mean[b]))
+ *   reduction 0 'none': elem [B][c] is written (part, loss unused, may be NULL);  1 'mean' / 2 'sum': loss[0] = the mean / sum of
+ *   the B c elements, through part [B] (scratch: the per-instance sums; elem unused, may be NULL)
+ *   backward: g is [B][c] (reduction 0) or one float; an element passes its gradient where margin - (y_pos - neg_mean) >= 0, as
+ *   torch's clamp_min does. */
+#define GH_RANK_MAX_ROWS (1 << 24)
+#define GH_RANK_MAX_NEG 4095
+int gh_rank_hinge_fwd(const float* y, int ld, int rows, int c, int num_neg, float margin, int reduction, float* neg_mean, float* elem,
+                      float* part, float* loss, gh_stream_t stream);
+int gh_rank_hinge_bwd(const float* y, int ld, int rows, int c, int num_neg, float margin, int reduction, const float* neg_mean,
+                      const float* g, float* dy, gh_stream_t stream);
+/* RankCrossEntropyLoss (matchzoo/losses/rank_cross_entropy_loss.py:29-38): the logits of instance b are its rows side by side,
+ * [pos | neg_1 | ... | neg_num_neg], (num_neg + 1) c of them, the labels the same entries of y_true (rows ldt floats apart):
+ *   loss[0] = -mean_b sum_j labels[b][j] * log_softmax(logits[b])[j], with log_softmax = x - max - log(sum exp(x - max)): finite
+ *   where the reference's log(softmax(x)) underflows to -inf (a logit some 104 below its row maximum).
+ *   lse [B] (saved for the backward) = the log-sum-exp of every instance; part [B] scratch.
+ *   backward: g one float; dy = g / B * (softmax * sum_j labels - labels); the labels are constants. */
+int gh_rank_ce_fwd(const float* y, int ld, const float* y_true, int ldt, int rows, int c, int num_neg, float* lse, float* part,
+                   float* loss, gh_stream_t stream);
+int gh_rank_ce_bwd(const float* y, int ld, const float* y_true, int ldt, int rows, int c, int num_neg, const float* lse, const float* g,
+                   float* dy, gh_stream_t stream);
+
 /* Everything the forward / backward need that is DERIVED from weight matrices, for n matrices in one launch (after the
  * optimiser step): dst_t[i] = src[i]^T as fp32 [cols][rows] (the backward's dX operands), and -- bf16 storage mode, any of the
  * two arrays or any entry may be NULL -- dst_w16[i] = bf16(src[i]) [rows][cols], dst_t16[i] = bf16(src[i]^T) [cols][rows]. */
