@@ -549,7 +549,7 @@ extern "C" int gh_att_flow_fwd(const float* c, const float* q, int ldc, int ldq,
   GH_REQUIRE(c && q && w_c && w_q && w_cq && b_c && b_q && b_cq && x && a && amax && m && beta && q2c, "att_flow_fwd: NULL argument");
   GH_REQUIRE(ldc >= d && ldq >= d && (long long)ldx >= 4LL * d, "att_flow_fwd: a leading dimension is smaller than its row");
   const size_t lds = (size_t)tile_lds_floats(af_plan(lq, d)) * sizeof(float);
-  if (int rc = lds_opt_in(af_fwd_tile_kernel, lds, "att_flow_fwd")) return rc;
+  if (int rc = lds_opt_in((const void*)af_fwd_tile_kernel, lds, "att_flow_fwd")) return rc;
   hipLaunchKernelGGL(af_fwd_tile_kernel, dim3(b * ((lc + 15) / 16)), dim3(AF_THREADS), lds, st, c, q, (long long)ldc, (long long)ldq, w_c,
                      w_q, w_cq, b_c, b_q, b_cq, lc, lq, d, x, (long long)ldx, a, amax, m);
   hipLaunchKernelGGL(af_fwd_batch_kernel, dim3(b, (d + AF_THREADS - 1) / AF_THREADS), dim3(AF_THREADS), 0, st, c, (long long)ldc, m, lc, d,
@@ -578,8 +578,8 @@ extern "C" int gh_att_flow_bwd(const float* c, const float* q, int ldc, int ldq,
   float* part_k = wsp.p + (size_t)b * d;
   const size_t lds_r = (size_t)tile_lds_floats(af_plan(lq, d)) * sizeof(float);
   const size_t lds_k = (size_t)key_lds_floats(key_plan(lc, d)) * sizeof(float);
-  if (int rc = lds_opt_in(af_bwd_row_kernel, lds_r, "att_flow_bwd")) return rc;
-  if (int rc = lds_opt_in(af_bwd_key_kernel, lds_k, "att_flow_bwd")) return rc;
+  if (int rc = lds_opt_in((const void*)af_bwd_row_kernel, lds_r, "att_flow_bwd")) return rc;
+  if (int rc = lds_opt_in((const void*)af_bwd_key_kernel, lds_k, "att_flow_bwd")) return rc;
   hipLaunchKernelGGL(af_bwd_batch_kernel, dim3(b), dim3(AF_THREADS), 0, st, c, (long long)ldc, g_x, (long long)ldg, beta, lc, d, dq2c, dm,
                      part_c);
   hipLaunchKernelGGL(af_bwd_row_kernel, dim3(b * ((lc + 15) / 16)), dim3(AF_THREADS), lds_r, st, c, q, (long long)ldc, (long long)ldq, w_c,

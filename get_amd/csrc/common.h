@@ -30,6 +30,8 @@ void set_error(const char* fmt, ...);
 
 #define GH_LAUNCH_CHECK() GH_CHECK_HIP(hipGetLastError())
 
+constexpr int MAX_R = 256;          // padded graph size supported by the one-workgroup-per-graph kernels
+constexpr int MAX_W = MAX_R / 64;
 inline int words_for(int r) { return (r + 63) / 64; }
 
 // A kernel variant or a tuning value is either what the product runs or it is removed (the measured-and-dropped ones live in
@@ -70,19 +72,30 @@ bool prof_enabled();
 void prof_begin(hipStream_t s, int tag);   // events are recorded only for tags selected by gh_profile_select
 void prof_end(int tag, double work, hipStream_t s);
 unsigned int* clamp_counter();      // four device counters of clamped out-of-range inputs on the current device (gh_clamp_events); NULL = allocation failed
+// Before a launch of `kernel` (the host-side function pointer) with `dynamic_lds` bytes of dynamic shared memory.  At or below the
+// 64 KB every kernel may have it does nothing.  Above, it refuses what the kernel's static LDS plus the request would take beyond
+// the 160 KB of a CU, and lifts the kernel's limit, once per kernel and device, to what is left beside its static LDS.
+// Returns 0, or the error code with the message (naming `who`) set.
+int lds_opt_in(const void* kernel, size_t dynamic_lds, const char* who);
 
 // Internal launchers used by the fused entry points, one group per implementing file.
 
-// ---- graph_ops.hip
+// ---- gsl_ops.hip
 // gh_scorer_gsl with the projection arriving as score_parts partial tensors, score_stride floats apart (wide cell outputs)
 int scorer_gsl_impl(const uint64_t* bits, const float* dinv, const float* vals, const int32_t* goff, int pads_collapsed, const float* feat,
                     const float* score_x, int score_parts, long long score_stride, const float* w_p, const float* gate, int n, int r, int h,
                     int k, float* score, uint64_t* keep, float drop_p, uint32_t drop_seed, hipStream_t stream);
+
+// ---- ragged_ops.hip
 int launch_ragged_plan(const int32_t* n_nodes, const int32_t* node_ids, int n, int r, int32_t* goff, int32_t* rowg, int32_t* src,
                        int32_t* cids, float* maskf, const int64_t* slot, int32_t* document, hipStream_t s, bool* scattered);   // *scattered: the document scatter rode along
+
+// ---- graph_build_ops.hip
 int launch_graph_build2(const int32_t* ta, const int32_t* la, int na, int ra, int32_t* ida, int32_t* nna, uint64_t* ba, float* da,
                         const int32_t* tb, const int32_t* lb, int nb, int rb, int32_t* idb, int32_t* nnb, uint64_t* bb, float* db,
                         int window, hipStream_t s);
+
+// ---- spmm_ops.hip
 struct ZeroFill { float* p0; long long n0; float* p1; long long n1; };      // n in floats, multiples of 4, 16-byte aligned pointers
 // goff != NULL: node-compact layout (include/get_hip.h) -- graph g owns rows [goff[g], goff[g+1]); m_real = goff[n]
 // zf: up to two float ranges the launch zero-fills on its way (the cell forward's padding rows of `a` and the scorer's partial

@@ -481,7 +481,6 @@ int launch_att_softmax_bwd(const float* right, const float* weights, const float
     const int nwg = ((M + rpw - 1) / rpw + 3) / 4;
     const size_t lds_rows = (size_t)4 * rpw * (2 * heads + 1) * 4;
     const int ptag = few_rows_tag(b, PROF_ATT_SOFTMAX_BWD);
-    prof_begin(s, ptag);
     static const void* const fns[8] = {(const void*)att_rows_bwd_kernel<1>, (const void*)att_rows_bwd_kernel<2>,
                                        (const void*)att_rows_bwd_kernel<3>, (const void*)att_rows_bwd_kernel<4>,
                                        (const void*)att_rows_bwd_kernel<5>, (const void*)att_rows_bwd_kernel<6>,
@@ -497,6 +496,8 @@ int launch_att_softmax_bwd(const float* right, const float* weights, const float
     int d4h = (dr / 4 + ranges - 1) / ranges;
     void* args[] = {(void*)&right, (void*)&weights, (void*)&g_att, (void*)&g_w, (void*)&rowg, (void*)&l, (void*)&dr, (void*)&heads,
                     (void*)&Mv, (void*)&rpwv, (void*)&dw_tmp, (void*)&dright, (void*)&d4h};
+    if (int rc = lds_opt_in(fn, lds_rows, "att_rows_bwd")) return rc;      // (256 rows per wave x 8 heads: 69 632 B)
+    prof_begin(s, ptag);
     (void)hipLaunchKernel(fn, dim3(nwg, ranges), dim3(256), args, lds_rows, s);
     prof_end(ptag, (right16 ? 6.0 : 8.0) * M * dr + 4.0 * (3.0 * M * heads + (double)b * dr * heads), s);
     GH_LAUNCH_CHECK();
@@ -505,13 +506,10 @@ int launch_att_softmax_bwd(const float* right, const float* weights, const float
   }
   GH_REQUIRE(right, "att_softmax_bwd: the per-pair kernel (few pairs / no row map) reads an fp32 right operand");
   const size_t lds = ((size_t)dr * heads + 2 * (size_t)l * heads) * 4;
-  GH_REQUIRE(lds <= 160 * 1024, "att_softmax_bwd: %zu B of LDS needed", lds);
   GH_REQUIRE(heads >= 1 && heads <= 8, "att_softmax_bwd: %d heads (1..8 supported)", heads);
   const void* fn = heads <= 2 ? (const void*)att_softmax_bwd_kernel<2> : heads <= 5 ? (const void*)att_softmax_bwd_kernel<5>
                                                                                    : (const void*)att_softmax_bwd_kernel<8>;
-  static bool attr[3] = {false, false, false};
-  const int ai = heads <= 2 ? 0 : heads <= 5 ? 1 : 2;
-  if (!attr[ai] && lds > 64 * 1024) { (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr[ai] = true; }
+  if (int rc = lds_opt_in(fn, lds, "att_softmax_bwd")) return rc;
   prof_begin(s, few_rows_tag(b, PROF_ATT_SOFTMAX_BWD));
   // few pairs (evidence level: one workgroup per claim): eight waves share the rows of a pair
   void* args[] = {(void*)&right, (void*)&weights, (void*)&g_att, (void*)&g_w, (void*)&goff, (void*)&l, (void*)&dr, (void*)&heads,

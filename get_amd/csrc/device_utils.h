@@ -1,7 +1,7 @@
 // Device helpers with one copy for every kernel file: wave and 16-lane reductions, the bf16 pack / widen of the bf16 storage
-// pipeline, the stateless dropout hash, the fast sigmoid / tanh, round-up and LDS-pitch arithmetic, the alignment test of the
-// float4 paths and the opt-in to more than 64 KB of LDS.  Included by the GEMM kernels (gemm.hip.h, and through it gemm_ops.hip,
-// cell_ops.hip, dense_ops.hip), the core streaming files (graph_ops.hip, stream_ops.hip, concat_att_ops.hip, eval_ops.hip) and
+// pipeline, the stateless dropout hash, the fast sigmoid / tanh, round-up and LDS-pitch arithmetic and the alignment test of the
+// float4 paths.  Included by the GEMM kernels (gemm.hip.h, and through it gemm_ops.hip,
+// cell_ops.hip, dense_ops.hip), the core streaming files (spmm_ops.hip, gsl_ops.hip, stream_ops.hip, concat_att_ops.hip, eval_ops.hip) and
 // the drop-in kernel files (attention_ops.hip, encoder_ops.hip, mha_ops.hip, rnn_ops.hip, bidaf_ops.hip, match_ops.hip).
 // score_tile.hip.h builds on it: the LDS staging and MFMA helpers of the three files that keep a 16-row score tile in LDS
 // (mha_ops.hip, bidaf_ops.hip, match_ops.hip).
@@ -75,13 +75,5 @@ __host__ __device__ inline int up16(int n) { return (n + 15) & ~15; }
 __host__ __device__ inline int pitch_kc(int n) { n = up4(n); return (n & 7) == 4 ? n : n + 4; }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// Before a launch with `lds` bytes of dynamic shared memory: refuses more than the 160 KB of a CU and lifts the kernel's
-// 64 KB default where it has to.  Returns 0, or the error code with the message set.
-template <typename K> int lds_opt_in(K kernel, size_t lds, const char* who) {
-  GH_REQUIRE(lds <= 160 * 1024, "%s: needs %zu bytes of LDS", who, lds);
-  if (lds > 64 * 1024) GH_CHECK_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  return 0;
-}
 
 }  // namespace gh

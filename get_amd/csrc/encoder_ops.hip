@@ -588,10 +588,10 @@ extern "C" int gh_gat_layer_fwd(const uint64_t* bits, const float* vals, const u
   const size_t lds = gat_lds_bytes(r, heads, 0);
   const bool v4 = f % 4 == 0 && aligned16(h) && aligned16(hp) && aligned16(out);
   if (v4) {
-    if (int rc = lds_opt_in(gat_aggregate_fwd_kernel<4>, lds, "gat_layer_fwd")) return rc;
+    if (int rc = lds_opt_in((const void*)gat_aggregate_fwd_kernel<4>, lds, "gat_layer_fwd")) return rc;
     hipLaunchKernelGGL(gat_aggregate_fwd_kernel<4>, dim3(n), dim3(256), lds, st, A, h, a, mode, s, stats, hp, out);
   } else {
-    if (int rc = lds_opt_in(gat_aggregate_fwd_kernel<1>, lds, "gat_layer_fwd")) return rc;
+    if (int rc = lds_opt_in((const void*)gat_aggregate_fwd_kernel<1>, lds, "gat_layer_fwd")) return rc;
     hipLaunchKernelGGL(gat_aggregate_fwd_kernel<1>, dim3(n), dim3(256), lds, st, A, h, a, mode, s, stats, hp, out);
   }
   GH_LAUNCH_CHECK();
@@ -611,7 +611,7 @@ extern "C" int gh_gat_layer_bwd(const uint64_t* bits, const float* vals, const u
   const int F = heads * f, m = n * r;
   const GatArgs A = gat_args(bits, vals, keep, n, r, heads, f, alpha, layer, drop_p, drop_seed);
   const size_t lds = gat_lds_bytes(r, heads, F);
-  if (int rc = lds_opt_in(gat_aggregate_bwd_kernel<1>, lds, "gat_layer_bwd")) return rc;
+  if (int rc = lds_opt_in((const void*)gat_aggregate_bwd_kernel<1>, lds, "gat_layer_bwd")) return rc;
   hipLaunchKernelGGL(gat_aggregate_bwd_kernel<1>, dim3(n), dim3(256), lds, st, A, h, a, mode, s, stats, hp, out, g, dh, da_part);
   GH_LAUNCH_CHECK();
   const int K = heads * 2 * f;

@@ -123,15 +123,13 @@ static hipError_t launch_cfg(const Launch& L, bool tn, hipStream_t s) {
     } else if constexpr (WM == 2 && WN == 2 && NI == 8 && MI == 4) {      // 128 x 256 tile (NT only)
       if (tn) return hipErrorInvalidValue;
       constexpr int kLds = 3 * (128 + 256) * 64;          // three K-loop stages (the epilogue staging fits inside)
-      static bool attr = false;
-      if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<2, 2, 8, 4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds); attr = true; }
+      if (lds_opt_in((const void*)gemm_nt_kernel<2, 2, 8, 4, 2>, kLds, "gemm_nt 128x256")) return hipErrorInvalidValue;
       hipLaunchKernelGGL((gemm_nt_kernel<2, 2, 8, 4, 2>), dim3(grid), dim3(256), kLds, s, L);
       launched = true;
     } else if constexpr (WM == 2 && WN == 4 && NI == 4 && MI == 8) {      // 256 x 256 x 64 tile, 8 waves, ping-pong K loop (NT only; gemm_nt_pp.hip.h)
       if (tn) return hipErrorInvalidValue;
       constexpr int kLds = 131072;                        // two K tiles of 64 KB (the epilogue staging fits inside)
-      static bool attr = false;
-      if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<2, 4, 4, 8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds); attr = true; }
+      if (lds_opt_in((const void*)gemm_nt_kernel<2, 4, 4, 8, 2>, kLds, "gemm_nt 256x256")) return hipErrorInvalidValue;
       hipLaunchKernelGGL((gemm_nt_kernel<2, 4, 4, 8, 2>), dim3(grid), dim3(512), kLds, s, L);
       launched = true;
     } else return hipErrorInvalidValue;
@@ -158,8 +156,7 @@ static hipError_t launch_cfg(const Launch& L, bool tn, hipStream_t s) {
       if (g_gemm_mode == 3) { L2 = L; pre = x3p_substitute(L2, s); }
       if (pre) {
         constexpr int kLds = 2 * (16 * 2 * WM * 64 + 16 * NI * WN * 112);      // two K-loop stages, B rows at the 112-byte pitch
-        static bool attr = false;
-        if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<WM, WN, NI, 2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds); attr = true; }
+        if (lds_opt_in((const void*)gemm_nt_kernel<WM, WN, NI, 2, 4>, kLds, "gemm_nt fp32x3p")) return hipErrorInvalidValue;
         hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, NI, 2, 4>), dim3(grid), dim3(WM * WN * 64), kLds, s, L2);
       } else
         hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, NI, 2, 3>), dim3(grid), dim3(WM * WN * 64), 0, s, L);
@@ -195,8 +192,7 @@ static hipError_t launch_tn_pp(const Launch& L, hipStream_t s) {
     prof_begin(s, tag);
   }
   constexpr int kLds = 131072;      // two K tiles of 64 KB
-  static bool attr = false;
-  if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_tn_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLds); attr = true; }
+  if (lds_opt_in((const void*)gemm_tn_pp_kernel, kLds, "gemm_tn_pp")) return hipErrorInvalidValue;
   hipLaunchKernelGGL(gemm_tn_pp_kernel, dim3(grid), dim3(512), kLds, s, L);
   prof_end(tag, flops, s);
   return hipGetLastError();

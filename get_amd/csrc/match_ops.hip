@@ -622,7 +622,7 @@ extern "C" int gh_soft_align_fwd(const float* q, const float* k, const float* v,
   GH_REQUIRE(ldq >= d && ldk >= d && ldv >= dv && (long long)ldo >= (fuse ? 4LL * d : (long long)dv),
              "soft_align_fwd: a leading dimension is smaller than its row");
   const size_t lds = (size_t)tile_lds_floats(mt_plan(lk, imax(d, dv))) * sizeof(float);
-  if (int rc = lds_opt_in(sa_fwd_kernel, lds, "soft_align_fwd")) return rc;
+  if (int rc = lds_opt_in((const void*)sa_fwd_kernel, lds, "soft_align_fwd")) return rc;
   hipLaunchKernelGGL(sa_fwd_kernel, dim3(b * ((lq + 15) / 16)), dim3(MT_THREADS), lds, st, q, k, v, (long long)ldq, (long long)ldk,
                      (long long)ldv, key_fill, row_zero, fill, fuse, lq, lk, d, dv, a, out, (long long)ldo);
   GH_LAUNCH_CHECK();
@@ -643,8 +643,8 @@ extern "C" int gh_soft_align_bwd(const float* q, const float* k, const float* v,
              "soft_align_bwd: a leading dimension is smaller than its row");
   const size_t lds_r = (size_t)tile_lds_floats(mt_plan(lk, imax(d, dv))) * sizeof(float);
   const size_t lds_k = (size_t)key_lds_floats(key_plan(lq, imax(d, dv))) * sizeof(float);
-  if (int rc = lds_opt_in(sa_bwd_row_kernel, lds_r, "soft_align_bwd")) return rc;
-  if (int rc = lds_opt_in(sa_bwd_key_kernel, lds_k, "soft_align_bwd")) return rc;
+  if (int rc = lds_opt_in((const void*)sa_bwd_row_kernel, lds_r, "soft_align_bwd")) return rc;
+  if (int rc = lds_opt_in((const void*)sa_bwd_key_kernel, lds_k, "soft_align_bwd")) return rc;
   hipLaunchKernelGGL(sa_bwd_row_kernel, dim3(b * ((lq + 15) / 16)), dim3(MT_THREADS), lds_r, st, q, k, v, (long long)ldq, (long long)ldk,
                      (long long)ldv, key_fill, row_zero, fuse, a, out, (long long)ldo, g, (long long)ldg, lq, lk, d, dv, ds, dq,
                      (long long)lddq);
@@ -695,7 +695,7 @@ extern "C" int gh_match_dot_fwd(const float* x, const float* y, int ldx, int ldy
   GH_REQUIRE(x && y && out && (!normalize || (ix && iy)), "match_dot_fwd: NULL argument");
   GH_REQUIRE(ldx >= d && ldy >= d, "match_dot_fwd: a leading dimension is smaller than its row");
   const size_t lds = (size_t)tile_lds_floats(mt_plan(r, d)) * sizeof(float);
-  if (int rc = lds_opt_in(md_fwd_kernel, lds, "match_dot_fwd")) return rc;
+  if (int rc = lds_opt_in((const void*)md_fwd_kernel, lds, "match_dot_fwd")) return rc;
   if (normalize) {
     const long long nx = (long long)b * l, ny = (long long)b * r;
     hipLaunchKernelGGL(inv_norm_kernel, dim3((unsigned)((nx + MT_WAVES - 1) / MT_WAVES)), dim3(MT_THREADS), 0, st, x, (long long)ldx, nx, d, ix);
@@ -715,8 +715,8 @@ extern "C" int gh_match_dot_bwd(const float* x, const float* y, int ldx, int ldy
   GH_REQUIRE(ldx >= d && ldy >= d, "match_dot_bwd: a leading dimension is smaller than its row");
   const size_t lds_x = (size_t)(tile_lds_floats(mt_plan(r, d))) * sizeof(float);
   const size_t lds_y = (size_t)(tile_lds_floats(mt_plan(l, d))) * sizeof(float);
-  if (int rc = lds_opt_in(md_bwd_kernel<false>, lds_x, "match_dot_bwd")) return rc;
-  if (int rc = lds_opt_in(md_bwd_kernel<true>, lds_y, "match_dot_bwd")) return rc;
+  if (int rc = lds_opt_in((const void*)md_bwd_kernel<false>, lds_x, "match_dot_bwd")) return rc;
+  if (int rc = lds_opt_in((const void*)md_bwd_kernel<true>, lds_y, "match_dot_bwd")) return rc;
   const float* nx = normalize ? ix : nullptr;
   const float* ny = normalize ? iy : nullptr;
   hipLaunchKernelGGL(md_bwd_kernel<false>, dim3(b * ((l + 15) / 16)), dim3(MT_THREADS), lds_x, st, x, y, (long long)ldx, (long long)ldy, nx,

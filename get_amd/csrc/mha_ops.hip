@@ -402,7 +402,7 @@ extern "C" int gh_mha_sdpa_fwd(const float* q, const float* k, const float* v, i
   GH_REQUIRE(ldq >= heads * dk && ldk >= heads * dk && ldv >= heads * dv && ldo >= heads * dv,
              "mha_sdpa_fwd: a leading dimension is smaller than heads * width");
   const size_t lds = (size_t)fwd_lds_floats(fwd_plan(lk, dk, dv)) * sizeof(float);
-  if (int rc = lds_opt_in(mha_fwd_kernel, lds, "mha_sdpa_fwd")) return rc;
+  if (int rc = lds_opt_in((const void*)mha_fwd_kernel, lds, "mha_sdpa_fwd")) return rc;
   hipLaunchKernelGGL(mha_fwd_kernel, dim3(b * ((lq + 15) / 16), heads), dim3(MHA_THREADS), lds, st, q, k, v, (long long)ldq,
                      (long long)ldk, (long long)ldv, mask, b, lq, lk, dk, dv, weights, out, (long long)ldo);
   GH_LAUNCH_CHECK();
@@ -420,8 +420,8 @@ extern "C" int gh_mha_sdpa_bwd(const float* q, const float* k, const float* v, i
              "mha_sdpa_bwd: a leading dimension is smaller than heads * width");
   const size_t lds_q = (size_t)fwd_lds_floats(fwd_plan(lk, dv, dk)) * sizeof(float);
   const size_t lds_k = (size_t)key_lds_floats(key_plan(lq, dk, dv)) * sizeof(float);
-  if (int rc = lds_opt_in(mha_bwd_q_kernel, lds_q, "mha_sdpa_bwd")) return rc;
-  if (int rc = lds_opt_in(mha_bwd_k_kernel, lds_k, "mha_sdpa_bwd")) return rc;
+  if (int rc = lds_opt_in((const void*)mha_bwd_q_kernel, lds_q, "mha_sdpa_bwd")) return rc;
+  if (int rc = lds_opt_in((const void*)mha_bwd_k_kernel, lds_k, "mha_sdpa_bwd")) return rc;
   hipLaunchKernelGGL(mha_bwd_q_kernel, dim3(b * ((lq + 15) / 16), heads), dim3(MHA_THREADS), lds_q, st, k, v, (long long)ldk,
                      (long long)ldv, weights, g_out, (long long)ldgo, g_weights, b, lq, lk, dk, dv, ds, dq, (long long)lddq);
   hipLaunchKernelGGL(mha_bwd_k_kernel, dim3(b * ((lk + 15) / 16), heads), dim3(MHA_THREADS), lds_k, st, q, (long long)ldq, weights,

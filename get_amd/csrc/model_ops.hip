@@ -1,6 +1,6 @@
 // Composite entry points: the whole GET forward / backward as ONE library call each (include/get_hip.h "a7"), the fused
 // cross-entropy and the one-call batch preparation.  Host-side chaining of the fused building blocks of cell_ops.hip / dense_ops.hip /
-// graph_ops.hip / stream_ops.hip / concat_att_ops.hip / ragged_ops.hip on two streams, plus the few small kernels that replace the at::native glue the
+// graph_build_ops.hip / spmm_ops.hip / gsl_ops.hip / stream_ops.hip / concat_att_ops.hip / ragged_ops.hip on two streams, plus the few small kernels that replace the at::native glue the
 // module-by-module path needed (lens casts, `* has`, torch.cat, index_copy_, the CE kernels).
 //
 // Why: issuing a training step module by module costs ~120 Python -> ctypes -> autograd round trips (~2.2 ms of host

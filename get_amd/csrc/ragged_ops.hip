@@ -1,5 +1,6 @@
 // Ragged claim <-> evidence helpers (gh_seg_*: offsets, broadcast, sum, pad, unpad), the masked mean of the claim vector
-// (gh_masked_mean_*) and the evidence-level assembly of the right operand and its mask (gh_evd_assemble_*).
+// (gh_masked_mean_*), the evidence-level assembly of the right operand and its mask (gh_evd_assemble_*) and the node-compact
+// layout plan (gh_ragged_plan, launch_ragged_plan).
 #include "../../include/get_hip.h"
 #include "common.h"
 
@@ -212,6 +213,84 @@ evd_assemble_bwd_kernel(const float* __restrict__ g, const int32_t* __restrict__
   }
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// node-compact layout plan.  goff = exclusive prefix sum of the node counts (one workgroup, n <= a few
+// thousand graphs), then one workgroup per graph fills the row maps.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(1024)
+ragged_scan_kernel(const int32_t* __restrict__ n_nodes, int n, int R, int32_t* __restrict__ goff) {
+  __shared__ int part[1024];
+  const int tid = threadIdx.x;
+  const int per = (n + 1023) / 1024;
+  const int lo = min(tid * per, n), hi = min(lo + per, n);
+  int sum = 0;
+  for (int g = lo; g < hi; ++g) sum += min(max(n_nodes[g], 0), R);
+  part[tid] = sum;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {          // Hillis-Steele inclusive scan of the per-thread sums
+    const int v = tid >= o ? part[tid - o] : 0;
+    __syncthreads();
+    part[tid] += v;
+    __syncthreads();
+  }
+  int run = part[tid] - sum;
+  for (int g = lo; g < hi; ++g) { goff[g] = run; run += min(max(n_nodes[g], 0), R); }
+  if (tid == 1023) goff[n] = part[1023];
+}
+
+__global__ void __launch_bounds__(256)
+ragged_fill_kernel(const int32_t* __restrict__ goff, const int32_t* __restrict__ node_ids, int n, int R,
+                   int32_t* __restrict__ rowg, int32_t* __restrict__ src, int32_t* __restrict__ cids,
+                   float* __restrict__ maskf) {
+  const int g = blockIdx.x;
+  const int row0 = goff[g], NR = goff[g + 1] - row0;
+  const int pad0 = goff[n] + g * R - row0 - NR;
+  for (int j = threadIdx.x; j < R; j += 256) {
+    const int row = j < NR ? row0 + j : pad0 + j;
+    rowg[row] = g;
+    src[row] = g * R + j;
+    const int id = (cids || maskf) ? node_ids[(size_t)g * R + j] : 0;
+    if (cids) cids[row] = id;
+    if (maskf) maskf[row] = id >= 1 ? 1.f : 0.f;       // the word attention's mask (doc >= 1, graph_based_semantic_structure.py:180)
+  }
+}
+
+// The plan in ONE launch for n <= 4096 graphs: every workgroup sums the node counts in front of its graph itself (n loads of
+// 4 bytes out of L2, 960 at the bench shape) instead of waiting for a one-workgroup scan kernel; optionally it also scatters
+// its graph's node ids into the padded `document` tensor (gh_get_prepare).
+__global__ void __launch_bounds__(256)
+ragged_plan1_kernel(const int32_t* __restrict__ n_nodes, const int32_t* __restrict__ node_ids, int n, int R,
+                    int32_t* __restrict__ goff, int32_t* __restrict__ rowg, int32_t* __restrict__ src, int32_t* __restrict__ cids,
+                    float* __restrict__ maskf, const int64_t* __restrict__ slot, int32_t* __restrict__ document) {
+  __shared__ int red[2][4];
+  const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int before = 0, all = 0;
+  for (int i = tid; i < n; i += 256) {
+    const int v = min(max(n_nodes[i], 0), R);
+    all += v;
+    if (i < g) before += v;
+  }
+  for (int o = 32; o > 0; o >>= 1) { before += __shfl_xor(before, o); all += __shfl_xor(all, o); }
+  if (lane == 0) { red[0][wave] = before; red[1][wave] = all; }
+  __syncthreads();
+  const int row0 = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+  const int total = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+  const int NR = min(max(n_nodes[g], 0), R);
+  if (tid == 0) { goff[g] = row0; if (g == n - 1) goff[n] = total; }
+  const int pad0 = total + g * R - row0 - NR;
+  const size_t dst = (slot && document) ? (size_t)slot[g] * R : 0;
+  for (int j = tid; j < R; j += 256) {
+    const int row = j < NR ? row0 + j : pad0 + j;
+    rowg[row] = g;
+    src[row] = g * R + j;
+    const int id = (cids || maskf || document) ? node_ids[(size_t)g * R + j] : 0;
+    if (cids) cids[row] = id;
+    if (maskf) maskf[row] = id >= 1 ? 1.f : 0.f;
+    if (slot && document) document[dst + j] = id;
+  }
+}
+
 }  // namespace gh
 
 using namespace gh;
@@ -265,6 +344,30 @@ extern "C" int gh_masked_mean_bwd(const float* g, const int32_t* ids, const floa
   return 0;
 }
 
+extern "C" int gh_ragged_plan(const int32_t* n_nodes, const int32_t* node_ids, int n, int r, int32_t* goff,
+                              int32_t* rowg, int32_t* src, int32_t* cids, float* maskf, gh_stream_t stream) {
+  GH_REQUIRE(r > 0 && r <= MAX_R, "ragged_plan: r=%d not in [1,%d]", r, MAX_R);
+  GH_REQUIRE((cids == nullptr && maskf == nullptr) || (node_ids != nullptr), "ragged_plan: cids / maskf need node_ids");
+  if (n <= 0) return 0;
+  return launch_ragged_plan(n_nodes, node_ids, n, r, goff, rowg, src, cids, maskf, nullptr, nullptr, (hipStream_t)stream, nullptr);
+}
+
+// slot / document: also scatter the node ids of graph g into document[slot[g]][:] (the composite batch preparation)
+int gh::launch_ragged_plan(const int32_t* n_nodes, const int32_t* node_ids, int n, int r, int32_t* goff, int32_t* rowg, int32_t* src,
+                           int32_t* cids, float* maskf, const int64_t* slot, int32_t* document, hipStream_t s, bool* scattered) {
+  if (scattered) *scattered = false;
+  if (n <= 4096 && (node_ids || !(slot && document))) {
+    hipLaunchKernelGGL(ragged_plan1_kernel, dim3(n), dim3(256), 0, s, n_nodes, node_ids, n, r, goff, rowg, src, cids, maskf, slot, document);
+    GH_LAUNCH_CHECK();
+    if (scattered) *scattered = slot && document;
+    return 0;
+  }
+  hipLaunchKernelGGL(ragged_scan_kernel, dim3(1), dim3(1024), 0, s, n_nodes, n, r, goff);
+  hipLaunchKernelGGL(ragged_fill_kernel, dim3(n), dim3(256), 0, s, goff, node_ids, n, r, rowg, src, cids, maskf);
+  GH_LAUNCH_CHECK();
+  return 0;      // (*scattered stays false: the document scatter, if any, is still the caller's)
+}
+
 extern "C" int gh_evd_assemble_fwd(const float* avg, const int32_t* offsets, const float* table, int table_rows, const void* sources,
                                    int sources_i64, const void* document, int document_i64, int b, int n_max, int xa, int ds,
                                    int r, float* right, float* mask, gh_stream_t stream) {
@@ -296,18 +399,10 @@ extern "C" int gh_evd_assemble_bwd(const float* g, const int32_t* offsets, const
   GH_REQUIRE(n_slots <= 38000, "evd_assemble_bwd: %d claim x evidence slots (max 38000 per call: split the batch)", n_slots);
   hipStream_t s = (hipStream_t)stream;
   const size_t lds_bytes = (size_t)((n_slots + 1) & ~1) * 4 + (size_t)((n_slots + 63) / 64) * 8;
-  if (lds_bytes > 48 * 1024) {
-    // The kernel's static LDS (its `earlier` flag) counts against the 160 KB of a CU as well: asking for all 160 KB as DYNAMIC
-    // memory was refused, and the refusal -- ignored here -- came back as the "invalid argument" of the launch check below, on the
-    // first call above 48 KB (tests/test_gpu_ragged_paths.py, 12 600 slots).  38 000 slots need 156 752 B.
-    constexpr int max_dynamic = 160 * 1024 - 64;
-    static bool attr = false;
-    if (!attr) {
-      GH_CHECK_HIP(hipFuncSetAttribute((const void*)evd_assemble_bwd_kernel<int64_t>, hipFuncAttributeMaxDynamicSharedMemorySize, max_dynamic));
-      GH_CHECK_HIP(hipFuncSetAttribute((const void*)evd_assemble_bwd_kernel<int32_t>, hipFuncAttributeMaxDynamicSharedMemorySize, max_dynamic));
-      attr = true;
-    }
-  }
+  // (38 000 slots need 156 752 B beside the kernel's static `earlier` flag)
+  if (int rc = lds_opt_in(sources_i64 ? (const void*)evd_assemble_bwd_kernel<int64_t> : (const void*)evd_assemble_bwd_kernel<int32_t>, lds_bytes,
+                          "evd_assemble_bwd"))
+    return rc;
   if (sources_i64)
     hipLaunchKernelGGL((evd_assemble_bwd_kernel<int64_t>), dim3(n_slots), dim3(256), lds_bytes, s, g, offsets,
                        (const int64_t*)sources, d_avg, d_table, n_slots, n_max, xa, ds, table_rows);

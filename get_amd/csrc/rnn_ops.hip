@@ -635,7 +635,7 @@ int rnn_launch(K kernel, const char* who, const float* w_hh0, const float* w_hh1
                gh_stream_t stream, A... args) {
   GH_REQUIRE(aligned16(w_hh0) && aligned16(w_hh1), "%s: w_hh must be 16-byte aligned", who);
   const size_t lds = (lds_floats + 2 * RNN_TILE) * sizeof(float);
-  if (int rc = lds_opt_in(kernel, lds, who)) return rc;
+  if (int rc = lds_opt_in((const void*)kernel, lds, who)) return rc;
   hipLaunchKernelGGL(kernel, dim3((n + RNN_TILE - 1) / RNN_TILE, dirs), dim3(RNN_THREADS), lds, (hipStream_t)stream, args...);
   GH_LAUNCH_CHECK();
   return 0;

@@ -1,8 +1,9 @@
 // The library's host-side state: the error message behind gh_last_error (set_error), the optional per-kernel event profiler
-// (prof_begin / prof_end, gh_profile_*), the per-device counters of clamped inputs (clamp_counter, gh_clamp_events) and
-// gh_abi_version.  Host code only: this file holds no kernel.
+// (prof_begin / prof_end, gh_profile_*), the per-device counters of clamped inputs (clamp_counter, gh_clamp_events), the one
+// opt-in to more than 64 KB of dynamic LDS (lds_opt_in) and gh_abi_version.  Host code only: this file holds no kernel.
 #include "../../include/get_hip.h"
 #include "common.h"
+#include <map>
 #include <mutex>
 #include <stdarg.h>
 #include <unordered_map>
@@ -64,6 +65,42 @@ unsigned int* clamp_counter() {
   if (hipMemset(p, 0, 4 * sizeof(unsigned int)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(p); return nullptr; }
   g_clamp_buf.emplace(dev, p);
   return p;
+}
+
+// ---------------------------------------------------------------------------- LDS opt-in (common.h)
+// The only place that raises hipFuncAttributeMaxDynamicSharedMemorySize.  A kernel's static LDS counts against the 160 KB of a CU
+// as well, so the limit asked for is 160 KB minus that (a flat 160 KB is refused for any kernel with a static word).  The table
+// holds the static LDS of every (kernel, device) that has been raised: the attribute is set once, later calls are a look-up.
+// (Keyed by the function pointer, not the kernel's type: the instantiations of one template share a type.)
+static std::mutex g_lds_mu;
+static std::map<std::pair<const void*, int>, size_t> g_lds_static;
+int lds_opt_in(const void* kernel, size_t dynamic_lds, const char* who) {
+  constexpr size_t kDefault = 64 * 1024, kCu = 160 * 1024;
+  if (dynamic_lds <= kDefault) return 0;
+  int dev = 0;
+  GH_CHECK_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lk(g_lds_mu);
+  const auto key = std::make_pair(kernel, dev);
+  auto it = g_lds_static.find(key);
+  const bool raised = it != g_lds_static.end();
+  size_t static_lds = 0;
+  if (raised) {
+    static_lds = it->second;
+  } else {
+    hipFuncAttributes fa;
+    const hipError_t e = hipFuncGetAttributes(&fa, kernel);
+    GH_REQUIRE(e == hipSuccess, "%s: cannot read the kernel's attributes: %s", who, hipGetErrorString(e));
+    static_lds = fa.sharedSizeBytes;
+  }
+  GH_REQUIRE(static_lds + dynamic_lds <= kCu, "%s: needs %zu bytes of dynamic LDS beside %zu static ones (a CU has %zu)", who,
+             dynamic_lds, static_lds, kCu);
+  if (!raised) {
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kCu - static_lds));
+    GH_REQUIRE(e == hipSuccess, "%s: raising the dynamic LDS limit to %zu bytes (%zu static) was refused: %s", who, kCu - static_lds,
+               static_lds, hipGetErrorString(e));
+    g_lds_static.emplace(key, static_lds);
+  }
+  return 0;
 }
 
 }  // namespace gh

@@ -1,239 +1,10 @@
-// Graph-side kernels: word-graph build, adjacency packing, bitmask aggregation (spmm),
-// fused word-scorer + GSL top-k.  All HBM-bound integer/bit work plus one streaming FMA pass;
-// no MFMA here by design.
+// Bitmask aggregation (spmm): the bit-walk slab kernel, the edge-list slab kernel and the bf16 aggregation on the matrix pipe.
+// Which of them a launch takes, and with what slabs, grid and LDS, is spmm_plan (spmm_plan.h): plain host arithmetic.
 #include "../../include/get_hip.h"
 #include "device_utils.h"
-#include <stdlib.h>
+#include "spmm_plan.h"
 
 namespace gh {
-
-constexpr int MAX_R = 256;          // padded graph size supported by the one-workgroup-per-graph kernels
-constexpr int MAX_W = MAX_R / 64;
-
-// ------------------------------------------------------------------------------------------------
-// a1  graph build (interactions.py:334-351).  One workgroup per text.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void graph_build_body(const int g, const int32_t* __restrict__ tokens, const int32_t* __restrict__ lengths, int R,
-                                                 int window, int32_t* __restrict__ node_ids, int32_t* __restrict__ n_nodes,
-                                                 uint64_t* __restrict__ bits, float* __restrict__ dinv) {
-  __shared__ int tok[MAX_R];
-  __shared__ int first[MAX_R];       // position of the first occurrence of tok[i]
-  __shared__ int node_of[MAX_R];     // node index of position i
-  __shared__ unsigned long long rows[MAX_R * MAX_W];
-  __shared__ int total;
-  const int tid = threadIdx.x;
-  const int W = (R + 63) / 64;
-  int len = lengths[g];
-  len = len < 0 ? 0 : (len > R ? R : len);
-  for (int i = tid; i < R; i += blockDim.x) tok[i] = (i < len) ? tokens[(size_t)g * R + i] : 0;
-  for (int i = tid; i < R * W; i += blockDim.x) rows[i] = 0ull;
-  __syncthreads();
-  // first occurrence (words_list.sort(key=raw_text.index), :335-336)
-  for (int i = tid; i < len; i += blockDim.x) {
-    int f = i;
-    const int t = tok[i];
-    for (int j = 0; j < i; ++j)
-      if (tok[j] == t) { f = j; break; }
-    first[i] = f;
-  }
-  __syncthreads();
-  // node index = number of first-occurrence positions before first[i]
-  for (int i = tid; i < len; i += blockDim.x) {
-    const int f = first[i];
-    int c = 0;
-    for (int j = 0; j < f; ++j) c += (first[j] == j);
-    node_of[i] = c;
-  }
-  if (tid == 0) {
-    int c = 0;
-    for (int j = 0; j < len; ++j) c += (first[j] == j);
-    total = c;
-  }
-  __syncthreads();
-  // node list, zero padded (:349)
-  for (int i = tid; i < R; i += blockDim.x) node_ids[(size_t)g * R + i] = 0;
-  __syncthreads();
-  for (int i = tid; i < len; i += blockDim.x)
-    if (first[i] == i) node_ids[(size_t)g * R + node_of[i]] = tok[i];
-  // window links over POSITIONS, accumulated on nodes (:342-344)
-  for (int i = tid; i < len; i += blockDim.x) {
-    const int ni = node_of[i];
-    const int lo = max(i - window + 1, 0), hi = min(i + window, len);
-    for (int j = lo; j < hi; ++j) {
-      const int nj = node_of[j];
-      atomicOr(&rows[ni * W + (nj >> 6)], 1ull << (nj & 63));
-    }
-  }
-  __syncthreads();
-  for (int i = tid; i < R; i += blockDim.x) {
-    int deg = 0;
-    for (int w = 0; w < W; ++w) {
-      const unsigned long long m = rows[i * W + w];
-      bits[((size_t)g * R + i) * W + w] = m;
-      deg += __popcll(m);
-    }
-    // D^-1/2 with zero-degree rows -> 0 (interactions.py:14-16)
-    dinv[(size_t)g * R + i] = deg > 0 ? (float)(1.0 / sqrt((double)deg)) : 0.f;
-  }
-  if (tid == 0) n_nodes[g] = total;
-}
-__global__ void __launch_bounds__(256)
-graph_build_kernel(const int32_t* __restrict__ tokens, const int32_t* __restrict__ lengths, int R, int window,
-                   int32_t* __restrict__ node_ids, int32_t* __restrict__ n_nodes, uint64_t* __restrict__ bits,
-                   float* __restrict__ dinv) {
-  graph_build_body(blockIdx.x, tokens, lengths, R, window, node_ids, n_nodes, bits, dinv);
-}
-// both sides of a batch in one launch (gh_get_prepare): workgroups [0, na) build the claims, the rest the evidences
-struct GraphSide { const int32_t* tokens; const int32_t* lengths; int R; int32_t* node_ids; int32_t* n_nodes; uint64_t* bits; float* dinv; };
-__global__ void __launch_bounds__(256)
-graph_build2_kernel(const GraphSide a, const GraphSide b, int na, int window) {
-  const bool first = (int)blockIdx.x < na;      // workgroup-uniform
-  const GraphSide& s = first ? a : b;
-  graph_build_body(first ? blockIdx.x : blockIdx.x - na, s.tokens, s.lengths, s.R, window, s.node_ids, s.n_nodes, s.bits, s.dinv);
-}
-
-// ------------------------------------------------------------------------------------------------
-// dense (N,R,R) adjacency -> packed bits + fp32 values.  One wave per row, ballot builds the word.
-// ------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void __launch_bounds__(256)
-adj_pack_kernel(const T* __restrict__ adj, int R, uint64_t* __restrict__ bits, float* __restrict__ vals) {
-  const int g = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int W = (R + 63) / 64;
-  for (int i = wave; i < R; i += 4) {
-    const size_t rb = ((size_t)g * R + i) * R;
-    for (int w = 0; w < W; ++w) {
-      const int j = w * 64 + lane;
-      float v = 0.f, vt = 0.f;
-      if (j < R) {
-        v = (float)adj[rb + j];
-        vals[rb + j] = v;
-        vt = (float)adj[((size_t)g * R + j) * R + i];
-      }
-      // the bit pattern is SYMMETRISED (A[i][j] != 0 or A[j][i] != 0): the transposed aggregation of the backward walks
-      // row i's bits and reads vals[j][i], so an entry present only in A^T must have its bit too; the extra entries
-      // carry the value 0 in `vals` and change no result
-      const unsigned long long m = __ballot(v != 0.f || vt != 0.f);
-      if (lane == 0) bits[((size_t)g * R + i) * W + w] = m;
-    }
-  }
-}
-
-// The reference fitter's de-padding (char_man_fitter_query_repr1.py:204-250: a Python loop over the claims slicing
-// `[:evd_count]` out of the padded (B, n_max, R) ids and (B, n_max, R, R) float64 adjacency, two host syncs per claim) plus the
-// packing of the adjacency and the node counts the node-compact plan needs, in ONE pass over the handed-over tensors:
-// workgroup (claim c, slot j) with j < counts[c] is pair p = sum(counts[:c]) + j; it narrows the ids, counts the real nodes
-// (id >= 1), packs its R x R block (as adj_pack_kernel) and checks what the node-compact layout assumes (ids prefix-shaped,
-// no edge on a padding node).  It also recognises the adjacency convert_text produces (interactions.py:11-18: D^-1/2 A D^-1/2
-// of a binary graph, A[i][j] = dinv[i] dinv[j] with dinv = 1 / sqrt(row degree)): such a block is fully described by its bit
-// rows + dinv (the kernels' "normalised" mode, 2 KB instead of 40 KB per graph); only for other blocks, or when `force_vals`
-// says that some graph of the batch needs them, the dense fp32 values are written.
-// stats = {pairs, real nodes, pairs that violate the layout assumption, pairs that are NOT normalised graphs, reserved}.
-template <typename TI>
-__global__ void __launch_bounds__(256)
-ref_depad_kernel(const int64_t* __restrict__ counts, int B, int n_max, int R, const TI* __restrict__ ids, const double* __restrict__ adj,
-                 int32_t* __restrict__ d_ids, uint64_t* __restrict__ bits, float* __restrict__ vals, float* __restrict__ dinv,
-                 int32_t* __restrict__ n_nodes, unsigned long long* __restrict__ stats, int force_vals) {
-  const int c = blockIdx.x / n_max, j = blockIdx.x % n_max;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  __shared__ int red[4];
-  __shared__ int s_real[256];
-  __shared__ float s_dinv[256];
-  __shared__ int s_bad, s_weighted;
-  const long long cnt_c = counts[c];
-  const int cc = cnt_c < 0 ? 0 : (cnt_c > n_max ? n_max : (int)cnt_c);
-  if (j >= cc) return;
-  // pair index: clamped counts of the claims before c (B is a few hundred at most)
-  int part = 0;
-  for (int i = tid; i < c; i += 256) { const long long v = counts[i]; part += v < 0 ? 0 : (v > n_max ? n_max : (int)v); }
-  for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
-  if (lane == 0) red[wave] = part;
-  if (tid == 0) { s_bad = 0; s_weighted = 0; }
-  __syncthreads();
-  const int p = red[0] + red[1] + red[2] + red[3] + j;
-  const size_t slot = (size_t)c * n_max + j;
-  // ids -> int32, real-node flags, node count
-  int real = 0;
-  if (tid < R) {
-    const long long id = (long long)ids[slot * R + tid];
-    d_ids[(size_t)p * R + tid] = (int32_t)id;
-    real = id >= 1 ? 1 : 0;
-  }
-  s_real[tid] = real;
-  int nn = real;
-  for (int o = 32; o > 0; o >>= 1) nn += __shfl_xor(nn, o);
-  __syncthreads();                      // (red is re-used: every thread has read it)
-  if (lane == 0) red[wave] = nn;
-  __syncthreads();
-  nn = red[0] + red[1] + red[2] + red[3];
-  int bad = (tid < R && real != (tid < nn ? 1 : 0)) ? 1 : 0;
-  // pass 1 over the block: bit rows (union of A's and A^T's patterns) and row degrees -> dinv as gh_graph_build computes it
-  const int W = (R + 63) / 64;
-  const double* ab = adj + slot * (size_t)R * R;
-  for (int i = wave; i < R; i += 4) {
-    int deg = 0;
-    for (int w = 0; w < W; ++w) {
-      const int jj = w * 64 + lane;
-      double v = 0.0, vt = 0.0;
-      if (jj < R) { v = ab[(size_t)i * R + jj]; vt = ab[(size_t)jj * R + i]; }
-      const unsigned long long m = __ballot((float)v != 0.f || (float)vt != 0.f);
-      if (lane == 0) bits[((size_t)p * R + i) * W + w] = m;
-      deg += __popcll(m);
-    }
-    if (deg > 0 && !s_real[i]) bad = 1;     // a padding node with edges: the node-compact layout would drop them
-    if (lane == 0) s_dinv[i] = deg > 0 ? (float)(1.0 / sqrt((double)deg)) : 0.f;
-  }
-  if (bad) s_bad = 1;
-  __syncthreads();
-  if (tid < R) dinv[(size_t)p * R + tid] = s_dinv[tid];
-  // pass 2 (the block is in L2 now): is every entry dinv[i] dinv[j] (to fp32 rounding of the fitter's float64 product)?
-  int weighted = 0;
-  for (int i = wave; i < R; i += 4) {
-    const float di = s_dinv[i];
-    for (int w = 0; w < W; ++w) {
-      const int jj = w * 64 + lane;
-      if (jj < R) {
-        const float v = (float)ab[(size_t)i * R + jj];
-        const float e = di * s_dinv[jj];
-        // (a pattern entry whose own value is 0 -- present on the transposed side only -- is not a normalised graph either)
-        const bool on = v != 0.f || (float)ab[(size_t)jj * R + i] != 0.f;
-        if (on && !(fabsf(v - e) <= 4e-7f * e)) weighted = 1;
-      }
-    }
-  }
-  if (weighted) s_weighted = 1;
-  __syncthreads();
-  if (s_weighted || force_vals) {
-    for (int i = wave; i < R; i += 4)
-      for (int jj = lane; jj < R; jj += 64) vals[((size_t)p * R + i) * R + jj] = (float)ab[(size_t)i * R + jj];
-  }
-  if (tid == 0) {
-    n_nodes[p] = nn;
-    atomicAdd(&stats[0], 1ull);
-    atomicAdd(&stats[1], (unsigned long long)nn);
-    if (s_bad) atomicAdd(&stats[2], 1ull);
-    if (s_weighted) atomicAdd(&stats[3], 1ull);
-  }
-}
-
-__global__ void __launch_bounds__(256)
-adj_unpack_kernel(const uint64_t* __restrict__ bits, const float* __restrict__ dinv, const float* __restrict__ vals,
-                  const uint64_t* __restrict__ keep, int R, float* __restrict__ adj) {
-  const int g = blockIdx.x;
-  const int W = (R + 63) / 64;
-  for (int it = threadIdx.x; it < R * R; it += blockDim.x) {
-    const int i = it / R, j = it % R;
-    bool on = (bits[((size_t)g * R + i) * W + (j >> 6)] >> (j & 63)) & 1ull;
-    if (on && keep) {
-      const bool ki = (keep[(size_t)g * W + (i >> 6)] >> (i & 63)) & 1ull;
-      const bool kj = (keep[(size_t)g * W + (j >> 6)] >> (j & 63)) & 1ull;
-      on = ki || kj;
-    }
-    float v = 0.f;
-    if (on) v = vals ? vals[((size_t)g * R + i) * R + j] : dinv[(size_t)g * R + i] * dinv[(size_t)g * R + j];
-    adj[((size_t)g * R + i) * R + j] = v;
-  }
-}
 
 // ------------------------------------------------------------------------------------------------
 // aggregation  y[g][i][:] (+)= sum_{j in N(i)} w_ij x[g][j][:]       (wrapper.py:192)
@@ -905,408 +676,65 @@ int launch_spmm(const uint64_t* bits, const float* dinv, const float* vals, cons
                 int m_real, const float* x, float* y, int n, int r, int h, int transpose, int accumulate, hipStream_t s, int bf16,
                 const ZeroFill* zfp, bool* zf_done) {
   if (zf_done) *zf_done = false;
-  GH_REQUIRE(r <= MAX_R, "spmm: padded graph size %d > %d", r, MAX_R);
+  GH_REQUIRE(r > 0 && r <= MAX_R, "spmm: padded graph size %d not in [1,%d]", r, MAX_R);
   GH_REQUIRE(vals || dinv, "spmm: need dinv or vals");
-  const int W = words_for(r);
   const bool v4 = (h % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) && ((reinterpret_cast<uintptr_t>(y) & 15) == 0);
   GH_REQUIRE(!bf16 || v4, "spmm: the bf16 variant needs h %% 4 == 0 and 16-byte aligned rows");
-  const int V = v4 ? 4 : 1;
-  const int hv = h / V;
-  // slab: <= 32 float4 (or 128 scalars) per row, as even as possible
-  // (sized so that a workgroup's slab stays under ~32 KB of LDS: four to five workgroups per CU, also at R = 200)
-  // round 4, A/B on one box: many graphs of <= 128 nodes (the bench step's 960 x 100) run 0.4 % faster per STEP on 24 KB slabs (five
-  // slabs of 15 float4 instead of four of 19), few graphs (218: the realistic step) 1 % slower
-  const int cap_kb = (goff && n >= 512 && r <= 128 && !bf16) ? 24 : 32;      // (node-compact layout only: the padded 100-row graphs run 58 -> 69 us on 24 KB slabs)   // measured per step: 48 KB -> 0.314 ms, 32 -> 0.288, 24 -> 0.294, 16 -> 0.344 (R = 100); R = 200: 0.60 -> 0.43
-  const int lds_cap = (cap_kb * 1024) / (r * (v4 ? 16 : 4));
-  const int slab_max = v4 ? (lds_cap < 32 ? (lds_cap < 4 ? 4 : lds_cap) : 32) : (lds_cap < 128 ? (lds_cap < 16 ? 16 : lds_cap) : 128);
-  const int nslab = (hv + slab_max - 1) / slab_max;
-  const int slab = (hv + nslab - 1) / nslab;
-  const size_t lds = ((((size_t)r * slab * V) + 3) & ~(size_t)3) * 4 + (size_t)r * W * 8 + (size_t)r * 4;
-  dim3 grid(n, nslab);
+  SpmmPlan p = spmm_plan(n, r, h, bf16 != 0, v4, goff != nullptr);
+  // No shape reaches the 64 KB a launch may have without an opt-in (tools/spmm_plan_sweep.cpp, DESIGN.md 4.23: at most 57 352 B on the
+  // edge list, 41 984 B on the bit walk): a slab rule that changes this fails here, not in the launch
+  GH_REQUIRE(p.lds <= 64 * 1024, "spmm: %zu B of LDS for r=%d, h=%d (the slab rule keeps a launch under 64 KB)", p.lds, r, h);
+  const dim3 grid(p.grid_x, p.grid_y);
   // algorithmic bytes: x in + y out (+ y in when accumulating) + bit rows + dinv (or the touched dense values)
   const double rows = goff ? (double)m_real : (double)n * r;
   const double alg_bytes = (2.0 + (accumulate ? 1.0 : 0.0)) * rows * h * (bf16 ? 2.0 : 4.0) +
-                           (double)n * ((double)r * W * 8.0 + (vals ? (double)r * r * 4.0 : (double)r * 4.0));
+                           (double)n * ((double)r * words_for(r) * 8.0 + (vals ? (double)r * r * 4.0 : (double)r * 4.0));
   const int ptag = few_rows_tag(n, PROF_SPMM);
   prof_begin(s, ptag);
-  if (bf16 && r <= 128 && h % 8 == 0) {
-    // bf16 rows: the aggregation as a dense product per graph on the matrix pipe (spmm_mfma_bf16_kernel), slabs of 128 columns,
-    // three of them per workgroup (few-graph launches: one)
-    constexpr int sc = 128, mseq = 3;
-    const int ns = (h + sc - 1) / sc;
-    int seq = n < 256 ? 1 : mseq;
-    if (seq > ns) seq = ns;
-    const int nchunk = (ns + seq - 1) / seq;
-    const unsigned short* x16 = reinterpret_cast<const unsigned short*>(x);
-    unsigned short* y16 = reinterpret_cast<unsigned short*>(y);
-    const dim3 mgrid(((n + 7) / 8) * 8 * nchunk);
+  switch (p.kind) {
+    case SPMM_MFMA_BF16: {
+      const unsigned short* x16 = reinterpret_cast<const unsigned short*>(x);
+      unsigned short* y16 = reinterpret_cast<unsigned short*>(y);
 #ifdef GH_MEASURE
-    static const int mdbg = measure_env("GH_SPMM_MFMA_NOSTORE", 0);
-    if (mdbg) accumulate |= 256 * mdbg;
+      static const int mdbg = measure_env("GH_SPMM_MFMA_NOSTORE", 0);
+      if (mdbg) accumulate |= 256 * mdbg;
 #endif
-    hipLaunchKernelGGL(spmm_mfma_bf16_kernel, mgrid, dim3(256), 0, s, bits, dinv, vals, keep, goff, x16, y16, r, h, transpose, accumulate, n, ns, seq);
-  } else if (v4 && r <= 256 && (!bf16 || hv % 2 == 0)) {
-    // edge-list slab kernel, LDS-DMA staging -- 62 us vs 69 us for the bit-walk slab kernel on 960 x 100 x 300 Zipf word graphs,
-    // 50 vs 61 us on hub-free graphs.  fp32 rows: two columns per thread.  bf16 rows: three -- a bf16 column is an 8-byte LDS read and
-    // four unpack instructions in front of its FMAs, the per-edge overhead (list entry, address) weighs more than in fp32: 960 graphs
-    // x h = 768, window 5: 148.6 / 126.9 / 120.0 / 122.2 / 126.2 us at 1 / 2 / 3 / 4 / 6 columns per thread (fewer, longer work items
-    // per row beyond three: the last round of items is thinly filled).  LDS pitch = slab columns.
-    // (removed, DESIGN 4.5: LDS-free gather variants -- thread-per-float4 / wave-per-row, measured equal or slower: with ~8K waves in
-    //  flight their sliding-window working set (~49 MB) thrashes the 32 MB of L2 -- and a graph-per-workgroup pipeline over two LDS
-    //  buffers, 74-85 us)
-    const int cap = 10 * r;                        // edges per graph the list holds (a window-5 word graph has <= 9 R)
-    int lslab = slab;
-    dim3 lgrid = grid;
-    if (bf16) {                                    // bf16 LDS image: 8 B per column -> twice the columns per slab, kept even
-      int smax = (cap_kb * 1024) / (r * 8);
-      smax = smax > 64 ? 64 : (smax < 4 ? 4 : smax);
-      smax &= ~1;
-      const int ns = (hv + smax - 1) / smax;
-      lslab = (((hv + ns - 1) / ns) + 1) & ~1;
-      lgrid = dim3(n, (hv + lslab - 1) / lslab);
+      hipLaunchKernelGGL(spmm_mfma_bf16_kernel, grid, dim3(256), 0, s, bits, dinv, vals, keep, goff, x16, y16, r, h, transpose, accumulate, n, p.nslab, p.seq);
+      break;
     }
-    // Rows that are whole 128-byte lines (h = 768: 1536 B in bf16, 3072 B in fp32): slabs of whole lines.  The even split above
-    // gives 40 bf16 columns = 320 B per row and slab -- 2.5 lines, every slab boundary inside a line that two workgroups fetch
-    // (configs[4] bf16, A/B on one box: five slabs of 40 columns 0.675 ms of aggregation per step, four slabs of 48 columns =
-    // 3 lines 0.607 ms; 64 columns = 51 KB of LDS per workgroup 0.91 ms).  Up to 40 KB of slab image per workgroup.
-    {
-      const int col_b = bf16 ? 8 : 16, per_line = 128 / col_b;            // float4 columns per 128-byte line
-      constexpr int line_kb = 40;
-      if (((size_t)h * (bf16 ? 2 : 4)) % 128 == 0 && hv % per_line == 0) {
-        int best = 0;
-        for (int c = per_line; c <= hv && (size_t)r * c * col_b <= (size_t)line_kb * 1024; c += per_line) best = c;
-        if (best >= 2 * per_line) {
-          const int ns = (hv + best - 1) / best;
-          int even = (((hv + ns - 1) / ns) + per_line - 1) / per_line * per_line;      // as even as whole lines allow
-          lslab = even;
-          lgrid = dim3(n, (hv + lslab - 1) / lslab);
-        }
+    case SPMM_LIST_F32:
+    case SPMM_LIST_BF16: {
+      const void* fn = bf16 ? (const void*)spmm_list_kernel<true, 3> : (const void*)spmm_list_kernel<false, 2>;
+      // split = 1: hub rows may hand their edge groups to items of their own (tool build: GH_SPMM_DBG << 8 runs one half of the kernel)
+      static const int split = 1 | (measure_env("GH_SPMM_DBG", 0) << 8);
+      ZeroFill zf = {nullptr, 0, nullptr, 0};
+      if (zfp && (zfp->n0 % 4 == 0) && (zfp->n1 % 4 == 0) && ((reinterpret_cast<uintptr_t>(zfp->p0) | reinterpret_cast<uintptr_t>(zfp->p1)) & 15) == 0) {
+        zf = *zfp;
+        if (zf_done) *zf_done = true;
       }
+      void* args[] = {(void*)&bits, (void*)&dinv, (void*)&vals, (void*)&keep, (void*)&goff, (void*)&x, (void*)&y, (void*)&r, (void*)&h,
+                      (void*)&p.slab, (void*)&p.cap, (void*)&transpose, (void*)&accumulate, (void*)&n, (void*)&p.nslab, (void*)&split, (void*)&p.seq,
+                      (void*)&zf};
+      (void)hipLaunchKernel(fn, grid, dim3(256), args, p.lds, s);
+      break;
     }
-    const size_t llds = (size_t)r * lslab * (bf16 ? 8 : 16) + (size_t)cap * 8 + (size_t)(r + 1) * 4 + (size_t)r * 4 + 4 + (size_t)r * 8;   // + item table
-    const void* fn = bf16 ? (const void*)spmm_list_kernel<true, 3> : (const void*)spmm_list_kernel<false, 2>;
-    static bool attr16 = false, attr32 = false;
-    bool& attr = bf16 ? attr16 : attr32;
-    if (!attr && llds > 64 * 1024) { (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
-    // slabs per workgroup, measured inside the bench step (ms of aggregation per step at 1 / 2 / all slabs per workgroup):
-    //   960 graphs, R = 100, h = 300 fp32 (4 slabs): 0.302 / 0.282 / 0.262;   640 graphs, R = 200 (8 slabs): 0.536 / 0.467 / 0.426;
-    //   960 graphs, h = 768 bf16 image, window 5 (5 slabs): 0.634 / 0.620 / 0.698 -- long per-slab work: the whole graph in one
-    //   workgroup leaves one thinly balanced round.  Few-graph launches (claim side) keep one slab per workgroup: latency.
-    // split = 1: hub rows may hand their edge groups to items of their own (tool build: GH_SPMM_DBG << 8 runs one half of the kernel)
-    static const int split = 1 | (measure_env("GH_SPMM_DBG", 0) << 8);
-    int ns_arg = (int)lgrid.y;
-    int seq = n < 256 ? 1 : (bf16 ? 2 : ns_arg);
-    if (seq > ns_arg) seq = ns_arg;
-    lgrid = dim3(((n + 7) / 8) * 8 * ((ns_arg + seq - 1) / seq), 1);
-    ZeroFill zf = {nullptr, 0, nullptr, 0};
-    if (zfp && (zfp->n0 % 4 == 0) && (zfp->n1 % 4 == 0) && ((reinterpret_cast<uintptr_t>(zfp->p0) | reinterpret_cast<uintptr_t>(zfp->p1)) & 15) == 0) {
-      zf = *zfp;
-      if (zf_done) *zf_done = true;
-    }
-    void* args[] = {(void*)&bits, (void*)&dinv, (void*)&vals, (void*)&keep, (void*)&goff, (void*)&x, (void*)&y, (void*)&r, (void*)&h,
-                    (void*)&lslab, (void*)&cap, (void*)&transpose, (void*)&accumulate, (void*)&n, (void*)&ns_arg, (void*)&split, (void*)&seq,
-                    (void*)&zf};
-    (void)hipLaunchKernel(fn, lgrid, dim3(256), args, llds, s);
-  } else if (bf16) {
-    static bool attrb = false;
-    if (!attrb && lds > 64 * 1024) { (void)hipFuncSetAttribute((const void*)spmm_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attrb = true; }
-    hipLaunchKernelGGL((spmm_kernel<4, true>), grid, dim3(256), lds, s, bits, dinv, vals, keep, goff, x, y, r, h, slab, transpose, accumulate);
-  } else if (v4) {
-    static bool attr4 = false;     // only raise the dynamic-LDS cap when a launch actually needs more than 64 KB
-    if (!attr4 && lds > 64 * 1024) { (void)hipFuncSetAttribute((const void*)spmm_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr4 = true; }
-    hipLaunchKernelGGL(spmm_kernel<4>, grid, dim3(256), lds, s, bits, dinv, vals, keep, goff, x, y, r, h, slab, transpose, accumulate);
-  } else {
-    static bool attr1 = false;
-    if (!attr1 && lds > 64 * 1024) { (void)hipFuncSetAttribute((const void*)spmm_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr1 = true; }
-    hipLaunchKernelGGL(spmm_kernel<1>, grid, dim3(256), lds, s, bits, dinv, vals, keep, goff, x, y, r, h, slab, transpose, accumulate);
+    case SPMM_WALK_BF16:
+      hipLaunchKernelGGL((spmm_kernel<4, true>), grid, dim3(256), p.lds, s, bits, dinv, vals, keep, goff, x, y, r, h, p.slab, transpose, accumulate);
+      break;
+    case SPMM_WALK_V4:
+      hipLaunchKernelGGL(spmm_kernel<4>, grid, dim3(256), p.lds, s, bits, dinv, vals, keep, goff, x, y, r, h, p.slab, transpose, accumulate);
+      break;
+    default:
+      hipLaunchKernelGGL(spmm_kernel<1>, grid, dim3(256), p.lds, s, bits, dinv, vals, keep, goff, x, y, r, h, p.slab, transpose, accumulate);
+      break;
   }
   prof_end(ptag, alg_bytes, s);
   GH_LAUNCH_CHECK();
   return 0;
 }
-
-// ------------------------------------------------------------------------------------------------
-// node-compact layout plan.  goff = exclusive prefix sum of the node counts (one workgroup, n <= a few
-// thousand graphs), then one workgroup per graph fills the row maps.
-// ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(1024)
-ragged_scan_kernel(const int32_t* __restrict__ n_nodes, int n, int R, int32_t* __restrict__ goff) {
-  __shared__ int part[1024];
-  const int tid = threadIdx.x;
-  const int per = (n + 1023) / 1024;
-  const int lo = min(tid * per, n), hi = min(lo + per, n);
-  int sum = 0;
-  for (int g = lo; g < hi; ++g) sum += min(max(n_nodes[g], 0), R);
-  part[tid] = sum;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {          // Hillis-Steele inclusive scan of the per-thread sums
-    const int v = tid >= o ? part[tid - o] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  int run = part[tid] - sum;
-  for (int g = lo; g < hi; ++g) { goff[g] = run; run += min(max(n_nodes[g], 0), R); }
-  if (tid == 1023) goff[n] = part[1023];
-}
-
-__global__ void __launch_bounds__(256)
-ragged_fill_kernel(const int32_t* __restrict__ goff, const int32_t* __restrict__ node_ids, int n, int R,
-                   int32_t* __restrict__ rowg, int32_t* __restrict__ src, int32_t* __restrict__ cids,
-                   float* __restrict__ maskf) {
-  const int g = blockIdx.x;
-  const int row0 = goff[g], NR = goff[g + 1] - row0;
-  const int pad0 = goff[n] + g * R - row0 - NR;
-  for (int j = threadIdx.x; j < R; j += 256) {
-    const int row = j < NR ? row0 + j : pad0 + j;
-    rowg[row] = g;
-    src[row] = g * R + j;
-    const int id = (cids || maskf) ? node_ids[(size_t)g * R + j] : 0;
-    if (cids) cids[row] = id;
-    if (maskf) maskf[row] = id >= 1 ? 1.f : 0.f;       // the word attention's mask (doc >= 1, graph_based_semantic_structure.py:180)
-  }
-}
-
-// The plan in ONE launch for n <= 4096 graphs: every workgroup sums the node counts in front of its graph itself (n loads of
-// 4 bytes out of L2, 960 at the bench shape) instead of waiting for a one-workgroup scan kernel; optionally it also scatters
-// its graph's node ids into the padded `document` tensor (gh_get_prepare).
-__global__ void __launch_bounds__(256)
-ragged_plan1_kernel(const int32_t* __restrict__ n_nodes, const int32_t* __restrict__ node_ids, int n, int R,
-                    int32_t* __restrict__ goff, int32_t* __restrict__ rowg, int32_t* __restrict__ src, int32_t* __restrict__ cids,
-                    float* __restrict__ maskf, const int64_t* __restrict__ slot, int32_t* __restrict__ document) {
-  __shared__ int red[2][4];
-  const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int before = 0, all = 0;
-  for (int i = tid; i < n; i += 256) {
-    const int v = min(max(n_nodes[i], 0), R);
-    all += v;
-    if (i < g) before += v;
-  }
-  for (int o = 32; o > 0; o >>= 1) { before += __shfl_xor(before, o); all += __shfl_xor(all, o); }
-  if (lane == 0) { red[0][wave] = before; red[1][wave] = all; }
-  __syncthreads();
-  const int row0 = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-  const int total = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-  const int NR = min(max(n_nodes[g], 0), R);
-  if (tid == 0) { goff[g] = row0; if (g == n - 1) goff[n] = total; }
-  const int pad0 = total + g * R - row0 - NR;
-  const size_t dst = (slot && document) ? (size_t)slot[g] * R : 0;
-  for (int j = tid; j < R; j += 256) {
-    const int row = j < NR ? row0 + j : pad0 + j;
-    rowg[row] = g;
-    src[row] = g * R + j;
-    const int id = (cids || maskf || document) ? node_ids[(size_t)g * R + j] : 0;
-    if (cids) cids[row] = id;
-    if (maskf) maskf[row] = id >= 1 ? 1.f : 0.f;
-    if (slot && document) document[dst + j] = id;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// top-k keep set from R scores held in LDS: rank by counting, ballot packs the 64-node words.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void topk_keep(const float* ss, int R, int k, uint64_t* keep_out, int tid) {
-  // one thread per node (R <= 256 = blockDim); wave w produces word w
-  bool kept = false;
-  if (tid < R) {
-    const float si = ss[tid];
-    int rank = 0;
-    for (int j = 0; j < R; ++j) {
-      const float sj = ss[j];
-      rank += (sj > si) || (sj == si && j < tid);
-    }
-    kept = rank < k;
-  }
-  const unsigned long long m = __ballot(kept);
-  const int W = (R + 63) / 64;
-  if ((tid & 63) == 0 && (tid >> 6) < W) keep_out[tid >> 6] = m;
-}
-
-// word scorer (GGNN 300->1, wrapper.py:167) + GSL top-k (:216-219), one workgroup per graph
-__global__ void __launch_bounds__(256)
-scorer_gsl_kernel(const uint64_t* __restrict__ bits, const float* __restrict__ dinv, const float* __restrict__ vals,
-                  const int32_t* __restrict__ goff, const float* __restrict__ feat, const float* __restrict__ xs_in,
-                  const float* __restrict__ w_p, const float* __restrict__ gate, int R, int H, int k, int pads_collapsed, float* __restrict__ score, uint64_t* __restrict__ keep, unsigned drop_thresh,
-                  float drop_scale, unsigned drop_seed, int xs_parts, long long xs_stride) {
-  __shared__ float xs[MAX_R];
-  __shared__ float ss[MAX_R];
-  const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int W = (R + 63) / 64;
-  // node-compact layout: real node j < NR sits in feature row goff[g] + j; padding node j >= NR of graph g in row
-  // goff[n] + (g*R - goff[g]) + (j - NR)  (all padding rows follow the real rows of the whole batch).  The padding
-  // nodes still compete in the top-k with their own (bias- and dropout-driven) scores, as in wrapper.py:216-219.
-  const int row0 = goff ? goff[g] : g * R;
-  const int NR = goff ? goff[g + 1] - row0 : R;
-  // pads_collapsed (evaluation mode: no dropout, so every padding row of the batch is the same vector): all padding
-  // nodes read the single representative row goff[n]
-  const int pad0 = goff ? goff[gridDim.x] + (pads_collapsed ? 0 : g * R - row0 - NR) : row0;
-  // x_j = feat_j . w_p   (proj, no bias)
-  const bool v4 = (H % 4 == 0) && ((reinterpret_cast<uintptr_t>(feat) & 15) == 0) && ((reinterpret_cast<uintptr_t>(w_p) & 15) == 0);
-  if (xs_in) {      // projection already done by the producing cell's epilogue (gh_ggnn_cell_fwd score_x): one float per node
-    if (tid < R) {      // (xs_parts > 1: one partial per column block of a wide cell output, added in block order)
-      const unsigned xr = (unsigned)(tid < NR ? row0 + tid : (pads_collapsed ? pad0 : pad0 + tid));
-      float v = xs_in[xr];
-      for (int pp = 1; pp < xs_parts; ++pp) v += xs_in[(size_t)pp * xs_stride + xr];
-      xs[tid] = v;
-    }
-  } else {
-  for (int j = wave; j < R; j += 4) {
-    float acc = 0.f;
-    const unsigned frow = (unsigned)(j < NR ? row0 + j : (pads_collapsed ? pad0 : pad0 + j));
-    const float* fg = feat + (size_t)frow * H;
-    if (v4) {
-      const float4* fr = reinterpret_cast<const float4*>(fg);
-      const float4* wr = reinterpret_cast<const float4*>(w_p);
-      for (int c = lane; c < H / 4; c += 64) {
-        float4 a = fr[c];
-        const float4 b = wr[c];
-        if (drop_thresh) a = drop4(a, drop_seed, frow * (unsigned)H + 4u * c, drop_thresh, drop_scale);
-        acc += a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
-      }
-    } else {
-      for (int c = lane; c < H; c += 64) {
-        float a = fg[c];
-        if (drop_thresh) a = drop_hash(drop_seed, frow * (unsigned)H + c) >= drop_thresh ? a * drop_scale : 0.f;
-        acc += a * w_p[c];
-      }
-    }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if (lane == 0) xs[j] = acc;
-  }
-  }
-  __syncthreads();
-  if (tid < R) {
-    const int i = tid;
-    float a = 0.f;
-    const float di = vals ? 0.f : dinv[(size_t)g * R + i];
-    for (int w = 0; w < W; ++w) {
-      unsigned long long m = bits[((size_t)g * R + i) * W + w];
-      while (m) {
-        const int j = (w << 6) + __builtin_ctzll(m);
-        m &= m - 1;
-        const float wt = vals ? vals[((size_t)g * R + i) * R + j] : di * dinv[(size_t)g * R + j];
-        a += wt * xs[j];
-      }
-    }
-    const float x = xs[i];
-    const float z = 1.f / (1.f + expf(-((gate[0] * a + gate[1]) + (gate[2] * x + gate[3]))));
-    const float r = 1.f / (1.f + expf(-((gate[4] * a + gate[5]) + (gate[6] * x + gate[7]))));
-    const float hh = tanhf((gate[8] * a + gate[9]) + (gate[10] * (r * x) + gate[11]));
-    const float sc = hh * z + x * (1.f - z);
-    ss[i] = sc;
-    score[(size_t)g * R + i] = sc;
-  }
-  __syncthreads();
-  topk_keep(ss, R, k, keep + (size_t)g * W, tid);
-}
-
-__global__ void __launch_bounds__(256)
-gsl_topk_kernel(const float* __restrict__ score, int R, int k, uint64_t* __restrict__ keep) {
-  __shared__ float ss[MAX_R];
-  const int g = blockIdx.x, tid = threadIdx.x;
-  if (tid < R) ss[tid] = score[(size_t)g * R + tid];
-  __syncthreads();
-  topk_keep(ss, R, k, keep + (size_t)g * ((R + 63) / 64), tid);
-}
-
 }  // namespace gh
 
 using namespace gh;
-
-extern "C" int gh_graph_build(const int32_t* tokens, const int32_t* lengths, int n_texts, int fixed_length,
-                              int window, int32_t* node_ids, int32_t* n_nodes, uint64_t* bits, float* dinv,
-                              gh_stream_t stream) {
-  GH_REQUIRE(fixed_length > 0 && fixed_length <= MAX_R, "graph_build: fixed_length %d not in [1,%d]", fixed_length, MAX_R);
-  GH_REQUIRE(window >= 1, "graph_build: window %d < 1", window);
-  if (n_texts <= 0) return 0;
-  prof_begin((hipStream_t)stream, PROF_GRAPH_BUILD);
-  hipLaunchKernelGGL(graph_build_kernel, dim3(n_texts), dim3(256), 0, (hipStream_t)stream, tokens, lengths,
-                     fixed_length, window, node_ids, n_nodes, bits, dinv);
-  prof_end(PROF_GRAPH_BUILD, (double)n_texts * (12.0 * fixed_length + 8.0 * fixed_length * words_for(fixed_length) + 8.0),
-           (hipStream_t)stream);
-  GH_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int gh_ragged_plan(const int32_t* n_nodes, const int32_t* node_ids, int n, int r, int32_t* goff,
-                              int32_t* rowg, int32_t* src, int32_t* cids, float* maskf, gh_stream_t stream) {
-  GH_REQUIRE(r > 0 && r <= MAX_R, "ragged_plan: r=%d not in [1,%d]", r, MAX_R);
-  GH_REQUIRE((cids == nullptr && maskf == nullptr) || (node_ids != nullptr), "ragged_plan: cids / maskf need node_ids");
-  if (n <= 0) return 0;
-  return launch_ragged_plan(n_nodes, node_ids, n, r, goff, rowg, src, cids, maskf, nullptr, nullptr, (hipStream_t)stream, nullptr);
-}
-
-// slot / document: also scatter the node ids of graph g into document[slot[g]][:] (the composite batch preparation)
-int gh::launch_ragged_plan(const int32_t* n_nodes, const int32_t* node_ids, int n, int r, int32_t* goff, int32_t* rowg, int32_t* src,
-                           int32_t* cids, float* maskf, const int64_t* slot, int32_t* document, hipStream_t s, bool* scattered) {
-  if (scattered) *scattered = false;
-  if (n <= 4096 && (node_ids || !(slot && document))) {
-    hipLaunchKernelGGL(ragged_plan1_kernel, dim3(n), dim3(256), 0, s, n_nodes, node_ids, n, r, goff, rowg, src, cids, maskf, slot, document);
-    GH_LAUNCH_CHECK();
-    if (scattered) *scattered = slot && document;
-    return 0;
-  }
-  hipLaunchKernelGGL(ragged_scan_kernel, dim3(1), dim3(1024), 0, s, n_nodes, n, r, goff);
-  hipLaunchKernelGGL(ragged_fill_kernel, dim3(n), dim3(256), 0, s, goff, node_ids, n, r, rowg, src, cids, maskf);
-  GH_LAUNCH_CHECK();
-  return 0;      // (*scattered stays false: the document scatter, if any, is still the caller's)
-}
-
-int gh::launch_graph_build2(const int32_t* ta, const int32_t* la, int na, int ra, int32_t* ida, int32_t* nna, uint64_t* ba, float* da,
-                            const int32_t* tb, const int32_t* lb, int nb, int rb, int32_t* idb, int32_t* nnb, uint64_t* bb, float* db,
-                            int window, hipStream_t s) {
-  GH_REQUIRE(ra > 0 && ra <= MAX_R && rb > 0 && rb <= MAX_R, "graph_build: fixed lengths %d / %d not in [1,%d]", ra, rb, MAX_R);
-  GH_REQUIRE(window >= 1, "graph_build: window %d < 1", window);
-  if (na + nb <= 0) return 0;
-  const GraphSide A = {ta, la, ra, ida, nna, ba, da}, B = {tb, lb, rb, idb, nnb, bb, db};
-  prof_begin(s, PROF_GRAPH_BUILD);
-  hipLaunchKernelGGL(graph_build2_kernel, dim3(na + nb), dim3(256), 0, s, A, B, na, window);
-  prof_end(PROF_GRAPH_BUILD, (double)na * (12.0 * ra + 8.0 * ra * words_for(ra) + 8.0) + (double)nb * (12.0 * rb + 8.0 * rb * words_for(rb) + 8.0), s);
-  GH_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int gh_adj_pack_f64(const double* adj, int n, int r, uint64_t* bits, float* vals, gh_stream_t stream) {
-  GH_REQUIRE(r > 0 && r <= MAX_R, "adj_pack: r=%d not in [1,%d]", r, MAX_R);
-  if (n <= 0) return 0;
-  hipLaunchKernelGGL(adj_pack_kernel<double>, dim3(n), dim3(256), 0, (hipStream_t)stream, adj, r, bits, vals);
-  GH_LAUNCH_CHECK();
-  return 0;
-}
-extern "C" int gh_adj_pack_f32(const float* adj, int n, int r, uint64_t* bits, float* vals, gh_stream_t stream) {
-  GH_REQUIRE(r > 0 && r <= MAX_R, "adj_pack: r=%d not in [1,%d]", r, MAX_R);
-  if (n <= 0) return 0;
-  hipLaunchKernelGGL(adj_pack_kernel<float>, dim3(n), dim3(256), 0, (hipStream_t)stream, adj, r, bits, vals);
-  GH_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int gh_ref_depad(const int64_t* counts, int b, int n_max, int r, const void* ids, int ids_i64, const double* adj,
-                            int32_t* d_ids, uint64_t* bits, float* vals, float* dinv, int32_t* n_nodes, int64_t* stats, int force_vals,
-                            gh_stream_t stream) {
-  GH_REQUIRE(r > 0 && r <= MAX_R, "ref_depad: r=%d not in [1,%d]", r, MAX_R);
-  GH_REQUIRE(b >= 0 && n_max > 0 && counts && ids && adj && d_ids && bits && vals && dinv && n_nodes && stats, "ref_depad: bad arguments");
-  GH_CHECK_HIP(hipMemsetAsync(stats, 0, 5 * sizeof(int64_t), (hipStream_t)stream));
-  if (b == 0) return 0;
-  if (ids_i64)
-    hipLaunchKernelGGL(ref_depad_kernel<int64_t>, dim3(b * n_max), dim3(256), 0, (hipStream_t)stream, counts, b, n_max, r,
-                       (const int64_t*)ids, adj, d_ids, bits, vals, dinv, n_nodes, (unsigned long long*)stats, force_vals);
-  else
-    hipLaunchKernelGGL(ref_depad_kernel<int32_t>, dim3(b * n_max), dim3(256), 0, (hipStream_t)stream, counts, b, n_max, r,
-                       (const int32_t*)ids, adj, d_ids, bits, vals, dinv, n_nodes, (unsigned long long*)stats, force_vals);
-  GH_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int gh_adj_unpack(const uint64_t* bits, const float* dinv, const float* vals, const uint64_t* keep, int n,
-                             int r, float* adj, gh_stream_t stream) {
-  GH_REQUIRE(r > 0 && r <= MAX_R, "adj_unpack: r=%d not in [1,%d]", r, MAX_R);
-  GH_REQUIRE(vals || dinv, "adj_unpack: need dinv or vals");
-  if (n <= 0) return 0;
-  hipLaunchKernelGGL(adj_unpack_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, bits, dinv, vals, keep, r, adj);
-  GH_LAUNCH_CHECK();
-  return 0;
-}
 
 extern "C" int gh_spmm(const uint64_t* bits, const float* dinv, const float* vals, const uint64_t* keep,
                        const int32_t* goff, int m_real, const float* x, float* y, int n, int r, int h, int transpose,
@@ -1321,42 +749,4 @@ extern "C" int gh_spmm_bf16(const uint64_t* bits, const float* dinv, const float
   if (n <= 0) return 0;
   GH_REQUIRE(h % 8 == 0, "spmm_bf16: h must be a multiple of 8");
   return launch_spmm(bits, dinv, vals, keep, goff, m_real, (const float*)x16, (float*)y16, n, r, h, transpose, accumulate, (hipStream_t)stream, 1);
-}
-
-extern "C" int gh_scorer_gsl(const uint64_t* bits, const float* dinv, const float* vals, const int32_t* goff,
-                             int pads_collapsed, const float* feat, const float* score_x, const float* w_p, const float* gate, int n, int r, int h, int k, float* score,
-                             uint64_t* keep, float drop_p, uint32_t drop_seed, gh_stream_t stream) {
-  return scorer_gsl_impl(bits, dinv, vals, goff, pads_collapsed, feat, score_x, 1, 0, w_p, gate, n, r, h, k, score, keep, drop_p, drop_seed,
-                         (hipStream_t)stream);
-}
-
-int gh::scorer_gsl_impl(const uint64_t* bits, const float* dinv, const float* vals, const int32_t* goff, int pads_collapsed, const float* feat,
-                        const float* score_x, int score_parts, long long score_stride, const float* w_p, const float* gate, int n, int r, int h,
-                        int k, float* score, uint64_t* keep, float drop_p, uint32_t drop_seed, hipStream_t stream) {
-  GH_REQUIRE(r > 0 && r <= MAX_R, "scorer_gsl: r=%d not in [1,%d]", r, MAX_R);
-  GH_REQUIRE(score_parts >= 1 && score_parts <= 16, "scorer_gsl: %d score partials", score_parts);
-  GH_REQUIRE(vals || dinv, "scorer_gsl: need dinv or vals");
-  if (n <= 0) return 0;
-  prof_begin((hipStream_t)stream, PROF_SCORER_GSL);
-  GH_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "scorer_gsl: dropout p=%f not in [0,1)", drop_p);
-  GH_REQUIRE(!(pads_collapsed && drop_p > 0.f), "scorer_gsl: collapsed padding rows are an evaluation-mode layout (no dropout)");
-  GH_REQUIRE(drop_p <= 0.f || (long long)n * r * (long long)h < (1LL << 32), "scorer_gsl: %d rows x %d columns exceed the dropout mask's 32-bit element index", n * r, h);
-  const double th = (double)drop_p * 4294967296.0;
-  const unsigned thresh = drop_p > 0.f ? (th >= 4294967295.0 ? 4294967295u : (unsigned)th) : 0u;
-  GH_REQUIRE((feat != nullptr) != (score_x != nullptr), "scorer_gsl: exactly one of feat / score_x");
-  hipLaunchKernelGGL(scorer_gsl_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, bits, dinv, vals, goff, feat, score_x,
-                     w_p, gate, r, h, k, (goff && pads_collapsed) ? 1 : 0, score, keep, thresh, 1.0f / (1.0f - drop_p), drop_seed,
-                     score_parts, score_stride);
-  prof_end(PROF_SCORER_GSL, (double)n * ((feat ? 4.0 * r * h : 4.0 * r) + 8.0 * r * words_for(r) + 8.0 * r + 8.0 * words_for(r)),
-           (hipStream_t)stream);
-  GH_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int gh_gsl_topk(const float* score, int n, int r, int k, uint64_t* keep, gh_stream_t stream) {
-  GH_REQUIRE(r > 0 && r <= MAX_R, "gsl_topk: r=%d not in [1,%d]", r, MAX_R);
-  if (n <= 0) return 0;
-  hipLaunchKernelGGL(gsl_topk_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, score, r, k, keep);
-  GH_LAUNCH_CHECK();
-  return 0;
 }

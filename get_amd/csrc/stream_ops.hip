@@ -523,16 +523,10 @@ int launch_head_bwd(const float* g_phi, const float* y0, const float* w1, const 
   GH_REQUIRE(C >= 1 && C <= 8 && Xl >= 0 && Xl <= E && d_y0, "head_bwd: bad sizes (C=%d Xl=%d E=%d)", C, Xl, E);
   const size_t lds = head_bwd_lds(B, H, C, E, w0);
   GH_REQUIRE(lds > 0, "head_bwd: B=%d, H=%d do not fit the kernel's LDS staging", B, H);
-  if (lds > 64 * 1024) {
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute((const void*)head_bwd_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute((const void*)head_bwd_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr = true;
-    }
-  }
+  const bool wide = head_bwd_wide(E, w0);
+  if (int rc = lds_opt_in(wide ? (const void*)head_bwd_kernel<4> : (const void*)head_bwd_kernel<1>, lds, "head_bwd")) return rc;
   const int dyf = 32 * H > 16 * 32 * 17 ? 32 * H : 16 * 32 * 17;
-  if (head_bwd_wide(E, w0))
+  if (wide)
     hipLaunchKernelGGL(head_bwd_kernel<4>, dim3((E + 63) / 64), dim3(256), lds, s, g_phi, y0, w1, w0, B, H, C, Xl, E, d_y0, dw1, db1, dx0,
                        dx0_accumulate, dx1, dyf);
   else

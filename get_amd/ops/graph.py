@@ -1,4 +1,5 @@
-"""Front of csrc/graph_ops.hip, cell_ops.hip and encoder_ops.hip: the packed adjacency and the node-compact plan, the
+"""Front of csrc/graph_build_ops.hip, spmm_ops.hip, gsl_ops.hip, ragged_ops.hip (the node-compact plan), cell_ops.hip and
+encoder_ops.hip: the packed adjacency and the node-compact plan, the
 aggregation, the GGNN cell, the word scorer with GSL, and the GAT / GCN encoders."""
 from __future__ import annotations
 

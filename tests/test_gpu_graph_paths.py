@@ -1,6 +1,7 @@
-"""Every dispatch path of the graph kernels (csrc/graph_ops.hip: gh_spmm / gh_spmm_bf16 with the edge-list, matrix-pipe
-and scalar aggregation kernels, gh_gsl_topk, gh_scorer_gsl, gh_graph_build, gh_adj_pack_* / gh_adj_unpack, gh_ragged_plan,
-gh_ref_depad, and gh_get_prepare of csrc/model_ops.hip) against plain numpy / float64 references on the CPU.
+"""Every dispatch path of the graph kernels (csrc/spmm_ops.hip: gh_spmm / gh_spmm_bf16 with the edge-list, matrix-pipe
+and scalar aggregation kernels; gsl_ops.hip: gh_gsl_topk, gh_scorer_gsl; graph_build_ops.hip: gh_graph_build, gh_adj_pack_* /
+gh_adj_unpack, gh_ref_depad; ragged_ops.hip: gh_ragged_plan; and gh_get_prepare of csrc/model_ops.hip) against plain numpy /
+float64 references on the CPU.
 
 The C-ABI entries are called directly.  Every output sits inside a larger allocation of its own, filled with NaN (floating
 point) or a sentinel (integers), at least 256 bytes of it on either side; what an entry documents as not written must
@@ -12,8 +13,8 @@ tests/util.py holds these restatements; tests/test_graph_restatements_cpu.py che
 Bounds: integer and bit outputs exact; fp32 aggregation and scorer scores 1e-4 of the float64 result's largest entry on
 every written element (tests.util._rel); bf16 aggregation |err| <= 2^-8 |ref| + 4e-6 (|A| |x| + |y0|) per element.
 
-No path counter exists for these kernels: the path named in a case's label follows from its shape by reading launch_spmm
-and launch_ragged_plan.  The evidence that a label is right is a mutation check on a scratch copy of the library (one
+No path counter exists for these kernels: the path named in a case's label follows from its shape by reading spmm_plan
+(csrc/spmm_plan.h, the arithmetic of launch_spmm) and launch_ragged_plan.  The evidence that a label is right is a mutation check on a scratch copy of the library (one
 change per path, the cases with that label fail), listed in DESIGN.md 4.8."""
 import functools
 from types import SimpleNamespace

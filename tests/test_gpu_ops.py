@@ -526,7 +526,7 @@ def test_compact_spmm_equals_padded(h):
 @pytest.mark.parametrize("h,n_graphs,window", [(768, 300, 5), (256, 40, 3), (520, 9, 5)])
 def test_spmm_bf16_is_the_fp32_aggregation_rounded_once(h, n_graphs, window):
     """gh_spmm_bf16 (the aggregation of the bf16 storage pipeline; R <= 128: a dense product per graph on the matrix pipe with the
-    fp32 edge weights split three ways into bf16, csrc/graph_ops.hip spmm_mfma_bf16_kernel) against gh_spmm on the same bf16 values held
+    fp32 edge weights split three ways into bf16, csrc/spmm_ops.hip spmm_mfma_bf16_kernel) against gh_spmm on the same bf16 values held
     in fp32: products exact to fp32 precision, fp32 accumulation, ONE rounding to bf16 -- so the result is the fp32 kernel's rounded
     once, except where the different fp32 summation order moves a sum across a rounding boundary: never more than one bf16 ulp, and
     for at most 0.2 % of the elements.  Padded and node-compact layout, with a keep set, transposed, accumulating.  Hub rows included."""
@@ -602,7 +602,7 @@ def test_spmm_bf16_weighted_asymmetric_adjacency(r):
 def test_spmm_hub_rows_split_over_work_items_match_dense_fp64(n_graphs):
     """Word graphs with a hub node (a token at every third position: degree ~2/3 of the nodes).  In the node-compact layout
     the aggregation kernel cuts such rows into 8-edge groups handled by separate work items whose partial sums meet in the
-    slab image's free rows (csrc/graph_ops.hip); the result must match a dense float64 product, the padded layout (which
+    slab image's free rows (csrc/spmm_ops.hip); the result must match a dense float64 product, the padded layout (which
     never splits) bit for bit, and the backward (transposed, accumulating launch) through autograd.  300 graphs: the
     one-workgroup-per-graph launch mode; 9: one slab per workgroup."""
     from get_amd import ops

@@ -231,3 +231,16 @@ def test_gemm_kernel_headers_stay_with_the_gemm_engine():
             if re.fullmatch(r"gemm.*\.hip\.h", pathlib.PurePath(inc).name):
                 assert allowed, f"{src.name} includes {inc}"
     assert "__global__" not in (csrc / "runtime_ops.hip").read_text()
+
+
+def test_one_lds_opt_in_and_one_max_r():
+    """The opt-in to more than 64 KB of dynamic LDS is written once (lds_opt_in, runtime_ops.hip: checked, aware of the kernel's
+    static LDS), so hipFuncSetAttribute appears in exactly one file of csrc/; and the padded graph size the one-workgroup-per-graph
+    kernels support, MAX_R, has one definition (common.h) for the files that share it."""
+    import pathlib
+    import re
+    csrc = pathlib.Path(__file__).resolve().parent.parent / "get_amd" / "csrc"
+    sources = sorted(list(csrc.glob("*.hip")) + list(csrc.glob("*.h")))
+    assert sources
+    assert [p.name for p in sources if "hipFuncSetAttribute" in p.read_text()] == ["runtime_ops.hip"]
+    assert [p.name for p in sources if re.search(r"\bMAX_R\s*=[^=]", p.read_text())] == ["common.h"]

@@ -341,7 +341,8 @@ def _gcn64(params, x, adj, layers, in_mask=None, p=0.0, relu_masks=None):
 
 
 # ----------------------------------------------------------------------------- graph restatements (numpy / float64, tests only)
-# Plain statements of what csrc/graph_ops.hip computes, used as the references of tests/test_gpu_graph_paths.py and
+# Plain statements of what csrc/graph_build_ops.hip, spmm_ops.hip, gsl_ops.hip and the node-compact plan of ragged_ops.hip compute,
+# used as the references of tests/test_gpu_graph_paths.py and
 # checked on their own, without any kernel, against the reference's goldens by tests/test_graph_restatements_cpu.py.
 def g_words(r):
     return (r + 63) // 64
