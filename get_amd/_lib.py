@@ -112,6 +112,13 @@ SIGNATURES = {
     "gh_rank_hinge_bwd": [_P, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P],
     "gh_rank_ce_fwd": [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P],
     "gh_rank_ce_bwd": [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P],
+    "gh_pair_l2_fwd": [_P, _P, _I, _I, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "gh_pair_l2_bwd": [_P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "gh_pair_l1_fwd": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
+    "gh_pair_l1_bwd": [_P, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P],
+    "gh_window_mean_fwd": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P],
+    "gh_window_mean_bwd": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P],
+    "gh_match_hist": [_P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
     # library-owned RCCL communicator (csrc/comm_ops.hip; librccl is dlopen'ed on first use)
     "gh_comm_unique_id": [_P],
     "gh_comm_init": [_P, _I, _I, _P],

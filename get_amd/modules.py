@@ -17,6 +17,9 @@ load unchanged:
                                                RNNDropout, StackedBRNN
   matchzoo/losses                              RankHingeLoss, RankCrossEntropyLoss
 
+(The tensor math outside the reference's modules -- the interaction helpers of torch_utils.py, layers.MovingAverage and the
+matching histogram -- is in get_amd/pairwise.py.)
+
 Adjacency arguments may be the reference's dense ``(N,R,R)`` tensors (any float dtype; packed once
 on the device, values kept exactly) or a native :class:`get_amd.ops.PackedAdj` from
 :func:`get_amd.ops.graph_build`.

@@ -844,6 +844,52 @@ int gh_rank_ce_fwd(const float* y, int ld, const float* y_true, int ldt, int row
 int gh_rank_ce_bwd(const float* y, int ld, const float* y_true, int ldt, int rows, int c, int num_neg, const float* lse, const float* g,
                    float* dy, gh_stream_t stream);
 
+/* ---- pairwise interaction helpers (csrc/pair_ops.hip): added under ABI 10, nothing existing changes ----
+ * Row operands take a leading dimension (floats between rows, batch i row r at (i * rows + r) * ld): column slices of a wider
+ * tensor are read in place.  Outputs and gradients are contiguous.  One writer per output element, no floating-point atomics.
+ *
+ * torch_utils.py:311-329 (cosine_distance, which is the Euclidean distance): a [bn][l][d] lda, b [bn][r][d] ldb,
+ *   out [bn][l][r] = sqrt(|inner| + eps), inner = (A2_l - 2 a_l.b_r) + B2_r in the reference's order of operations, so that
+ *   coincident rows give rounding noise under the root, as there.  a2 [bn][l], b2 [bn][r] receive the squared row norms and
+ *   sgn [bn][l][r] one byte per entry, sign(inner) in {-1, 0, 1}: the backward needs it and out does not hold it.
+ *   Limits: l, r <= 1024, d <= 2048, eps finite and >= 0. */
+int gh_pair_l2_fwd(const float* a, const float* b, int lda, int ldb, float eps, int bn, int l, int r, int d, float* a2, float* b2,
+                   float* out, int8_t* sgn, gh_stream_t stream);
+/* Backward from g [bn][l][r] with the forward's out and sgn: w = g 0.5 / out sgn (sign(0) = 0: such an entry sends nothing),
+ * da_l = 2 a_l sum_r w_lr - 2 sum_r w_lr b_r, db_r = 2 b_r sum_l w_lr - 2 sum_l w_lr a_l; da [bn][l][d], db [bn][r][d]. */
+int gh_pair_l2_bwd(const float* a, const float* b, int lda, int ldb, const float* out, const int8_t* sgn, const float* g, int bn, int l,
+                   int r, int d, float* da, float* db, gh_stream_t stream);
+/* torch_utils.py:332-348 (l1_distance): out [bn][l][r] = sum_k |a_lk - b_rk|, summed in k order, without the reference's
+ * [bn][l][r][d] difference tensor.  Limits: l, r <= 1024, d <= 2048. */
+int gh_pair_l1_fwd(const float* a, const float* b, int lda, int ldb, int bn, int l, int r, int d, float* out, gh_stream_t stream);
+/* Backward from g [bn][l][r]: da_lk = sum_r g_lr sign(a_lk - b_rk) in r order, db_rk = -sum_l g_lr sign(a_lk - b_rk) in l order,
+ * with sign(0) = 0 as the backward of torch's norm(p=1) has it. */
+int gh_pair_l1_bwd(const float* a, const float* b, int lda, int ldb, const float* g, int bn, int l, int r, int d, float* da, float* db,
+                   gh_stream_t stream);
+/* torch_utils.py:292-308 (moving_average), :351-376 (_get_doc_context_copacrr) and layers.py:42-66 (MovingAverage):
+ *   out [bn][lo][d], lo = l + left + right - w + 1 >= 1, out[t] = mask[t] / w * sum_{s = t - left}^{t - left + w - 1} x[s] over
+ *   x [bn][l][d] ldx, the `left` rows before and the `right` rows behind the sequence counting as zeros (F.pad).  Every window
+ *   is summed directly, in row order, never from a running prefix.  mask [bn][lo] fp32 or NULL; a row whose mask is 0 is an
+ *   exact zero.  moving_average / MovingAverage: left = right = 0, mask = NULL; the context form of window c: left = c / 2,
+ *   right = c - c / 2 - 1, w = c.  Limits: w, left, right <= 1024, l <= 2^20, d <= 2048. */
+int gh_window_mean_fwd(const float* x, int ldx, const float* mask, int bn, int l, int d, int w, int left, int right, float* out,
+                       gh_stream_t stream);
+/* Backward from g [bn][lo][d] ldg: dx [bn][l][d], dx[s] = 1 / w * sum_{t = s + left - w + 1}^{s + left} mask[t] g[t] over the
+ * existing t: the same window, reversed, over the masked g.  A row whose mask is 0 sends an exact zero. */
+int gh_window_mean_bwd(const float* g, int ldg, const float* mask, int bn, int l, int d, int w, int left, int right, float* dx,
+                       gh_stream_t stream);
+/* matchzoo/preprocessors/units/matching_histogram.py:44-60 for a batch (data_generator/callbacks/histogram.py:37-65):
+ *   table [v][d] ldt, inv_norm [v] or NULL (the products are then scaled by inv_norm[left id] inv_norm[right id]),
+ *   ids_left [bn][lq], ids_right [bn][ld], len_right [bn] int32 (clamped into [0, ld]); out [bn][lq][bins] fp32.
+ *   Entry (i, bin) starts from 1 and counts the right ids j < len_right of its sample with
+ *   int((table[left_i].table[right_j] + 1) / 2 * (bins - 1)) == bin, truncated toward zero and clamped into [0, bins - 1];
+ *   right ids at or beyond len_right are ignored, every left id counts.  mode 0 (CH) leaves the counts, 1 (NH) divides by the row
+ *   total bins + len_right, 2 (LCH) takes the logarithm.  The rows are gathered through the ids, no gathered copy is written.
+ *   An id outside [0, v) fails the call (flag: one int32 of device scratch; the verdict is read back before anything is read
+ *   through an id, so the call synchronises the stream).  No backward.  Limits: lq, ld <= 1024, d <= 2048, bins <= 256. */
+int gh_match_hist(const float* table, int ldt, const float* inv_norm, int v, int d, const int32_t* ids_left, const int32_t* ids_right,
+                  const int32_t* len_right, int bn, int lq, int ld, int bins, int mode, float* out, int32_t* flag, gh_stream_t stream);
+
 /* Everything the forward / backward need that is DERIVED from weight matrices, for n matrices in one launch (after the
  * optimiser step): dst_t[i] = src[i]^T as fp32 [cols][rows] (the backward's dX operands), and -- bf16 storage mode, any of the
  * two arrays or any entry may be NULL -- dst_w16[i] = bf16(src[i]) [rows][cols], dst_t16[i] = bf16(src[i]^T) [cols][rows]. */
