@@ -1,9 +1,10 @@
-// What the GEMM engine (gemm_ops.hip) offers the layers built on it (cell_ops.hip, dense_ops.hip): a layer fills in Problems,
-// hands them to a Batch and reads the Batch's outcome.  The only GEMM header a layer file includes; every definition that is
-// not inline here lives in gemm_ops.hip, next to the kernels it launches.  workspace_for() and gemm_mode() are in common.h.
+// What the GEMM engine offers the layers built on it (cell_ops.hip, dense_ops.hip): a layer fills in Problems, hands them to a
+// Batch and reads the Batch's outcome.  The only GEMM header a layer file includes, and it brings in no kernel: Batch's methods
+// live in gemm_batch.hip (host code: the plans of gemm_plan.h), the three launchers below in gemm_ops.hip next to their kernels.
+// workspace_for() and gemm_mode() are in common.h.
 #pragma once
 #include "common.h"
-#include "gemm.hip.h"      // Problem, Launch, EPI_*, make_problem / make_seg_* (its kernel is a template: nothing is instantiated here)
+#include "gemm_types.h"    // Problem, Launch, EPI_*, make_problem / make_seg_*
 
 namespace gh {
 
@@ -46,7 +47,7 @@ struct Batch {
   bool split_done = false;      // the last flush took the few-row split-K plan (its finish kernel applied the problems' row epilogues)
   float* g_ws = nullptr;        // the stream's split-K scratch (workspace_for), NULL = none registered
   size_t g_ws_bytes = 0;
-  // 64 x 160 fp32 tile (launch_cfg<2, 2, 5>): half the accumulators -> <= 128 VGPRs -> FOUR workgroups per CU instead of three,
+  // 64 x 160 fp32 tile (CFG_64x160): half the accumulators -> <= 128 VGPRs -> FOUR workgroups per CU instead of three,
   // two column blocks per 300-wide problem.  More resident workgroups run more of the neighbours' epilogue streams underneath
   // the K loops: launches with stream-heavy epilogues gain, plain-store launches lose (prototype, tools/glds_proto.hip NHALF:
   // h-gate-like epilogue K = 300: 62.6 -> 68.2 TF, K = 600: 87.7 -> 90.5; plain store: 92.4 -> 88.7).  Chosen per call site.
@@ -56,22 +57,21 @@ struct Batch {
   // att_softmax_fwd, adds the partials in block order -- deterministic).  0 = whole rows only.
   long long e_block_stride = 0;
 
- private:      // the engine's own state and plans (gemm_ops.hip)
+ private:      // the engine's own state (gemm_batch.hip; the plans themselves: gemm_plan.h)
   Launch L;
   bool tn, big;
   hipStream_t s;
   int k_total = 0;
   float* cs_out[GH_MAX_PROBLEMS] = {nullptr};
   float* cs_out2[GH_MAX_PROBLEMS] = {nullptr};
-  bool wide = false;      // 128 x 256 bf16 tile (launch_cfg<2, 2, 8, 4>)
-  bool wide256 = false;   // 256 x 256 x 64 bf16 tile, 8 waves, ping-pong K loop (launch_cfg<2, 4, 4, 8>)
+  bool wide = false;      // 128 x 256 bf16 tile (CFG_128x256)
+  bool wide256 = false;   // 256 x 256 x 64 bf16 tile, 8 waves, ping-pong K loop (CFG_256x256)
   // weight gradients of the bf16 storage pipeline on the 256 x 256 x 64 ping-pong tile (gemm_tn_pp.hip.h): the batch's problems stay
   // WHOLE outputs (no 320-column blocks), the kernel walks their 256 x 256 tiles.  Decided by the first problem of a launch.
   bool tn_pp = false;
-  bool tn_pp_ok(const Problem& p) const;
   void reset();
   hipError_t launch_any();
-  bool nt_split_plan();
+  bool nt_split();
 };
 
 // EPI_ATT as a pass of its own over a stored product t [M][ha] (in place): t = tanh(t + u[urow ? urow[m] : m / l]), e = W2 t.

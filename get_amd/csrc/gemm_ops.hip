@@ -1,8 +1,10 @@
-// The GEMM engine: every instantiation of the grouped MFMA GEMM kernels, the fp32x3 weight images, the split-K workspace with its
-// reduce / finish kernels, and Batch's tile and split-K planning.  gemm_batch.h is what it offers the layers built on it
-// (cell_ops.hip: GGNN cell; dense_ops.hip: concat attention, linear layers), which hold no kernel and compile in seconds.
+// The GEMM engine's kernels: every instantiation of the grouped MFMA GEMM kernels with launch_cfg / launch_tn_pp, the fp32x3 weight
+// images, the split-K workspace registry, the reduce / finish / nn kernels and their launchers.  What runs on them is decided elsewhere:
+// Batch's methods are in gemm_batch.hip and its arithmetic in gemm_plan.h, which this file does not include -- they reach the kernels
+// through the launchers of gemm_engine.h.  gemm_batch.h is what the engine offers the layers (cell_ops.hip, dense_ops.hip).
 #include "../../include/get_hip.h"
 #include "gemm_batch.h"
+#include "gemm_engine.h"
 #include "device_utils.h"
 #include "gemm_nt.hip.h"
 #include "gemm_tn.hip.h"
@@ -11,49 +13,6 @@
 
 namespace gh {
 
-static bool s_lds_bad(const Problem& p) { return p.seg[0].lda % 8 || p.seg[0].ldb % 8; }
-// fast-path preconditions of gemm_nt.hip.h (NT: both operands contraction-contiguous) and gemm_tn.hip.h (TN); both LDS-DMA
-// tool build: GH_FASTOK_DEBUG=1 names the rule that sent a launch to the generic kernel (seg >= 0: and that segment's sizes)
-static void fast_why(int rule, int prob, const Problem* p = nullptr, int seg = -1) {
-  static const bool dbg = measure_env("GH_FASTOK_DEBUG", 0) != 0;
-  if (!dbg) return;
-  fprintf(stderr, "gemm: generic kernel (fast_ok rule %d, problem %d)\n", rule, prob);
-  if (p && seg >= 0) fprintf(stderr, "   seg %d lda %d M %d N %d K %d\n", seg, p->seg[seg].lda, p->M, p->N, p->seg[seg].K);
-}
-static bool fast_ok(const Launch& L, bool tn) {
-  for (int i = 0; i < L.nprob; ++i) {
-    const Problem& p = L.p[i];
-    const int ns = tn ? 1 : p.nseg;
-    for (int j = 0; j < ns; ++j) {
-      const Seg& s = p.seg[j];
-      if (!s.vecA || !s.vecB || s.gatherB || s.K < 4) { fast_why(1, i); return false; }
-      if (tn && s.gatherA) { fast_why(2, i); return false; }
-    }
-    if (p.elt && tn && (p.M % 8 || p.N % 8 || s_lds_bad(p))) { fast_why(3, i); return false; }
-    if (!tn) {  // operands are addressed through buffer descriptors: 31-bit byte offsets
-      for (int j = 0; j < p.nseg; ++j) {
-        if (4.0 * (double)p.seg[j].ldb * (double)p.N >= 2147483648.0) { fast_why(4, i); return false; }
-        if (!p.seg[j].gatherA && 4.0 * (double)p.seg[j].lda * (double)p.M >= 2147483648.0) { fast_why(5, i, &p, j); return false; }   // (gathered tables: < 2 GB by contract)
-      }
-    }
-    if (tn) {
-      const Seg& s = p.seg[0];
-      if (4.0 * (double)s.lda * (double)s.K >= 2147483648.0 || 4.0 * (double)s.ldb * (double)s.K >= 2147483648.0) { fast_why(6, i); return false; }
-    }
-    if (p.N % 4 || p.N < 4 || p.ldc % 4 || !aligned16(p.C)) { fast_why(7, i); return false; }
-    if (tn && (p.M % 4 || p.M < 4)) { fast_why(8, i); return false; }
-    if ((p.bias && !aligned16(p.bias)) || (p.bias2 && !aligned16(p.bias2)) || (p.out1 && !aligned16(p.out1)) || (p.in0 && !aligned16(p.in0)) || (p.in1 && !aligned16(p.in1)))
-      { fast_why(9, i); return false; }
-    if (p.epi == EPI_ATT && (!aligned16(p.u) || p.ldu % 4 || !aligned16(p.w2))) { fast_why(10, i); return false; }
-    if (p.epi == EPI_TANH_H && p.w2 && !aligned16(p.w2)) { fast_why(11, i); return false; }
-    if (p.epi == EPI_GATE_PRE && (tn || !p.in0 || !p.in1 || !p.in2 || !p.out1 || !p.out2 || !aligned16(p.in2) || !aligned16(p.out2) ||
-                                  (p.gin && !aligned16(p.gin)))) { fast_why(12, i); return false; }
-  }
-  return true;
-}
-// bf16 weight-gradient GEMM on the 256 x 256 x 64 ping-pong tile (gemm_tn_pp.hip.h): K-chunk rows from which a batch of whole-output
-// problems takes it (below: the 128 x 320 tile, gemm_tn_bf16_kernel<2, 2, 10, 4>)
-constexpr int TN_PP_ROWS = 16384;
 static bool wants_dropout(const Launch& L) {
   for (int i = 0; i < L.nprob; ++i)
     if (L.p[i].drop_mode) return true;
@@ -72,9 +31,9 @@ static bool x3p_substitute(Launch& L, hipStream_t s);
 int gemm_mode() { return g_gemm_mode; }
 long long generic_launches() { return g_path_counts[1]; }
 
+// fast, grid: gemm_plan.h fast_rule / gemm_grid, computed by the caller (gemm_batch.hip)
 template <int WM, int WN, int NI, int MI = 2>
-static hipError_t launch_cfg(const Launch& L, bool tn, hipStream_t s) {
-  const bool fast = fast_ok(L, tn);
+static hipError_t launch_cfg(const Launch& L, bool tn, bool fast, int grid, hipStream_t s) {
   {
     double fl = 0.0;
     for (int i = 0; i < L.nprob; ++i)
@@ -82,10 +41,6 @@ static hipError_t launch_cfg(const Launch& L, bool tn, hipStream_t s) {
     g_path_counts[fast ? 0 : 1] += 1;
     if (!fast && fl >= 1e9) g_path_counts[2] += 1;
   }
-  const int n_outer = tn ? L.ksplit : L.m_tiles;
-  const int n_inner = tn ? L.m_tiles * L.nprob : L.nprob * L.ksplit;
-  const bool nt_few = !tn && L.m_tiles < 8 && fast;      // gemm_nt.hip.h: linear work decode for launches of fewer than 8 row tiles
-  const int grid = nt_few ? n_outer * n_inner : 8 * ((n_outer + 7) / 8) * n_inner;
   if (grid <= 0) return hipSuccess;
   // profiler row: by the SIZE of the launch, not by the tile configuration it runs on -- the activation-sized single-problem
   // launches that the occupancy rule moves to the 32-row tile belong with the big GEMMs (booked under
@@ -181,7 +136,7 @@ static hipError_t launch_cfg(const Launch& L, bool tn, hipStream_t s) {
 }
 
 // bf16 weight gradients on the 256 x 256 x 64 ping-pong tile: one workgroup per CU, work items dealt to the XCDs in runs (L.per each)
-static hipError_t launch_tn_pp(const Launch& L, hipStream_t s) {
+hipError_t launch_tn_pp(const Launch& L, hipStream_t s) {
   const int grid = 8 * L.per;
   if (grid <= 0) return hipSuccess;
   g_path_counts[0] += 1;
@@ -331,8 +286,6 @@ Workspace workspace_for(hipStream_t s) {
   return it != g_ws_stream.end() ? it->second : g_ws_default;
 }
 
-struct ReduceItem { const float* ws; float* out; int I, J, ldc, ks; long long stride; };
-struct ReduceArgs { ReduceItem it[3 * GH_MAX_PROBLEMS]; int n; };     // tiles of <= 8 problems + up to two bias-gradient outputs each
 
 __global__ void __launch_bounds__(256)
 reduce_partials_kernel(const ReduceArgs R) {
@@ -485,22 +438,6 @@ nn_accumulate_kernel(const NnArgs R_byval) {
   }
 }
 
-// Second half of an NT GEMM that was split over K: sum the partial tiles, then apply the problem's real epilogue
-// (any of gemm.hip.h's row epilogues).  One wave per output row.
-struct FinishItem {
-  const float* ws; long long stride; int ks; int M, N, epi, accumulate, ldc;
-  float* C; const float* bias; const float* bias2; float* out1; const float* in0; const float* in1;
-  const float* u; const float* w2; float* e; int ldu, R, heads;
-  const int32_t* rowg;
-};
-
-// Two shapes.  split = 1 (few-row products with many partials: the head's K = 3556 product has 55): one WORKGROUP per output
-// row, the four waves each sum a quarter of the partial tiles (eight 16-byte loads in flight per lane), the quarter sums meet
-// in LDS in wave order (fixed summation order: deterministic) and wave 0 applies the epilogue -- one wave per row walked all
-// `ks` partials alone, 14 dependent memory round trips = 18 us for the head; four waves need 4.  split = 0: one wave per
-// row, four rows per workgroup (few partials, many rows).
-struct FinishArgs { FinishItem it[GH_MAX_PROBLEMS]; int n; int split; };
-
 __global__ void __launch_bounds__(256)
 nt_finish_kernel(const FinishArgs F) {
   const FinishItem& it = F.it[blockIdx.y];
@@ -602,296 +539,25 @@ nt_finish_kernel(const FinishArgs F) {
   }
 }
 
-// ---- Batch (declared in gemm_batch.h, with the comments on its knobs): tile choice, column blocks, split-K plans -------------
-bool Batch::tn_pp_ok(const Problem& p) const {
-  if (!tn || !p.elt || p.nseg != 1 || g_ws == nullptr || p.epi != EPI_ATOMIC) return false;
-  const Seg& sg = p.seg[0];
-  if (sg.gatherA || sg.gatherB || !sg.vecA || !sg.vecB || sg.K < TN_PP_ROWS) return false;
-  if (p.M % 256 || p.N % 256 || p.ldc % 4 || (reinterpret_cast<uintptr_t>(p.C) & 15)) return false;
-  return (size_t)sg.K * (size_t)sg.lda * 2 < ((size_t)1 << 31) && (size_t)sg.K * (size_t)sg.ldb * 2 < ((size_t)1 << 31);
-}
-Batch::Batch(bool tn_, int rows_hint, hipStream_t s_, bool wide_bf16, int site, int n_hint) : tn(tn_), s(s_) {
-  const Workspace w = workspace_for(s_);
-  g_ws = w.p; g_ws_bytes = w.bytes;
-  big = tn_ || rows_hint >= 8192;      // 64x320 tile (2x2 waves) for the activation-sized GEMMs, 32x320 (1x4) for few-row ones
-  bm = big ? 64 : 32;
-  bn = 320;
-  if (wide_bf16 && big && !tn_) { wide = true; bm = 128; bn = 256; }
-  // 256 x 256 x 64 / 8 waves, one workgroup per CU, ping-pong K loop + software-pipelined epilogue (gemm_nt_pp.hip.h, round 6):
-  // the default for activation-sized launches of the bf16 storage pipeline -- configs[4], B = 32: gemm_big 4.25 -> 3.09 ms per
-  // step, 128.1 -> 148.6 K pairs/s.  (Round 3's 256 x 256 tile -- the 128 x 256 tile's K loop on 8 waves, 32-deep stages --
-  // measured 0.200 against 0.207: not the tile size but the loop structure is the lever.)  Launches below 32 768 rows (fewer
-  // than 1.5 workgroups per CU) keep the 128 x 256 tile.
-  constexpr int tile256_rows = 32768;
-  if (wide && rows_hint >= tile256_rows) { wide256 = true; bm = 256; }
-  const bool less_pad = n_hint > 0 && (n_hint + 159) / 160 * 160 < (n_hint + 319) / 320 * 320;
-  // launches whose 64 x 320 grid would not fill one round of 768 workgroup slots (realistic evidence counts: 14 208 rows = 222
-  // row tiles) get twice the workgroups on 1024 slots: 99.0 -> 102.0 K pairs/s on the Snopes-histogram step at B = 32
-  const bool thin = rows_hint <= 24576;
-  if (site > 0 && big && !tn_ && !wide && g_gemm_mode == 0 && (((NARROW_DEFAULT >> (site - 1)) & 1) || less_pad || thin)) { narrow = true; bn = 160; }
-  // (launches without a call-site id, e.g. the attention's t product with its head scores, keep the 64 x 320 tile)
-  reset();
-}
-void Batch::reset() {
-  L.nprob = 0; L.m_tiles = 0; L.ksplit = 1; L.kchunk = 0; k_total = 0; L.n_tiles = 0; L.per = 0;
-  static const int dbg = measure_env("GH_DBG", 0);      // (tool build: DBG_* bits, gemm.hip.h)
-  L.dbg = dbg;
-  for (int i = 0; i < GH_MAX_PROBLEMS; ++i) cs_out[i] = cs_out2[i] = nullptr;
-}
 
-void Batch::add(const Problem& p) {
-  // row reductions need whole rows -- except the scorer's single dot product, which two column blocks may add up (e_atomic)
-  const bool scorer_blocks = p.epi == EPI_TANH_H && p.w2 && p.N > bn && narrow && p.N <= 2 * bn;
-  const bool att_blocks = p.epi == EPI_ATT && p.N > bn && e_block_stride > 0;
-  // ... or, with a partial buffer per block (e_block_stride), any number of them: the scorer kernel adds the partials in block order
-  const bool scorer_parts = p.epi == EPI_TANH_H && p.w2 && p.N > bn && !scorer_blocks && e_block_stride > 0;
-  if ((p.epi == EPI_ATT || (p.epi == EPI_TANH_H && p.w2)) && p.N > bn && !scorer_blocks && !att_blocks && !scorer_parts) { err = hipErrorInvalidValue; return; }
-  if (tn) {
-    const bool want = tn_pp_ok(p);
-    if (L.nprob > 0 && want != tn_pp) flush();      // (a launch is one kernel: problems of the other kind start the next one)
-    if (L.nprob == 0) tn_pp = want;
-  }
-  const int bn = tn_pp ? (1 << 30) : this->bn;
-  for (int n0 = 0; n0 < p.N; n0 += bn) {
-    Problem q = p;
-    q.N = (p.N - n0 < bn) ? p.N - n0 : bn;
-    auto adv = [](const float* ptr, size_t elems, bool bf) { return (const float*)((const char*)ptr + elems * (bf ? 2 : 4)); };
-    for (int i = 0; i < q.nseg; ++i) {
-      if (tn) {
-        q.seg[i].B = adv(q.seg[i].B, (size_t)n0, q.elt);
-        q.seg[i].vecB = q.elt ? (((reinterpret_cast<uintptr_t>(q.seg[i].B) & 15) == 0) && q.seg[i].ldb % 8 == 0 && q.N % 8 == 0)
-                              : vec_ok(q.seg[i].B, q.seg[i].ldb, q.N);
-      } else {
-        q.seg[i].B = adv(q.seg[i].B, (size_t)n0 * q.seg[i].ldb, q.elt);       // B is [N][ldb]: a column block of C is a row block of B
-      }
-    }
-    q.C = (float*)adv(q.C, (size_t)n0, q.io & 1);
-    q.drop_col0 = p.drop_col0 + n0;
-    if (q.bias) q.bias += n0;
-    if (q.bias2) q.bias2 += n0;
-    if (q.out1) q.out1 = (float*)adv(q.out1, (size_t)n0, q.io & 2);
-    if (q.in0) q.in0 = adv(q.in0, (size_t)n0, q.io & 4);
-    if (q.in1) q.in1 = adv(q.in1, (size_t)n0, q.io & 8);
-    if (q.c32) q.c32 += n0;
-    if (q.gin) q.gin += n0;
-    if (q.in2) q.in2 = adv(q.in2, (size_t)n0, q.io & 16);
-    if (q.out2) q.out2 = (float*)adv(q.out2, (size_t)n0, q.io & 32);
-    if (scorer_blocks) { q.w2 += n0; q.e_atomic = 1; }
-    if (scorer_parts) { q.w2 += n0; q.e = p.e + (size_t)(n0 / bn) * (size_t)e_block_stride; q.e_atomic = 2; }
-    if (att_blocks) { q.w2 += n0; q.u += n0; q.e = p.e + (size_t)(n0 / bn) * (size_t)e_block_stride; q.e_atomic = 2; }      // (2: own partial buffer, plain stores)
-    if (L.nprob == GH_MAX_PROBLEMS) flush();
-    L.p[L.nprob++] = q;
-    const int bm_eff = tn_pp ? 256 : (tn && q.elt) ? 128 : bm;      // (bf16 TN: the 128 x 320 tile; all problems of a TN launch share the storage mode)
-    const int mt = (q.M + bm_eff - 1) / bm_eff;
-    if (mt > L.m_tiles) L.m_tiles = mt;
-    if (tn_pp && (q.N + 255) / 256 > L.n_tiles) L.n_tiles = (q.N + 255) / 256;
-    if (q.seg[0].K > k_total) k_total = q.seg[0].K;
+// ---- the launchers of gemm_engine.h ----------------------------------------------------------------------------------------
+hipError_t launch_gemm(GemmConfig cfg, const Launch& L, bool tn, bool fast, int grid, hipStream_t s) {
+  switch (cfg) {
+    case CFG_32x320: return launch_cfg<1, 4, 5>(L, tn, fast, grid, s);
+    case CFG_64x320: return launch_cfg<2, 2, 10>(L, tn, fast, grid, s);
+    case CFG_64x160: return launch_cfg<2, 2, 5>(L, tn, fast, grid, s);
+    case CFG_128x256: return launch_cfg<2, 2, 8, 4>(L, tn, fast, grid, s);
+    case CFG_256x256: return launch_cfg<2, 4, 4, 8>(L, tn, fast, grid, s);
+    default: return hipErrorInvalidValue;      // (CFG_TN_PP: launch_tn_pp)
   }
 }
-
-void Batch::flush() {
-  if (L.nprob == 0 || err != hipSuccess) { reset(); return; }
-  if (tn) {
-    const int n_inner = L.m_tiles * L.nprob;
-    constexpr int target = 2304;
-    int ks = (target + n_inner - 1) / n_inner;   // three resident rounds of 256 CUs x 3 workgroups (measured on the bench step: 1152 -> 2.06 ms,
-                                                 // 1536 -> 1.95, 2304 -> 1.86, 3072 -> 1.84 but more partials to reduce; one round 20 % slower)
-    // shortest K chunk: 256 rows (fp32).  bf16 storage, wide outputs (h = 768: 64 x 320 partial tiles of 80 KB each): a single
-    // 768 x 768 product split into 64 chunks writes and re-reads more partial-tile bytes than it streams operands
-    constexpr int min_rows16 = 4096;      // (A/B on configs[4]: 256 / 1024 / 2048 / 4096 rows = 106.76 / 106.72 / 106.81 / 107.17 K pairs/s)
-    const int min_rows = L.p[0].elt ? min_rows16 : 256;
-    const int ks_max = (k_total / min_rows > 1) ? k_total / min_rows : 1;
-    if (ks > ks_max) ks = ks_max;
-    if (ks < 1) ks = 1;
-    // The K chunks are dealt round-robin to the 8 XCDs (chunk c runs on XCD c % 8, gemm_tn.hip.h): a chunk count that is
-    // not a multiple of 8 leaves some XCDs one chunk (1 / 8 of their work at 65 chunks) more than the others.  Measured on
-    // the bench step (A/B, one box): 65 chunks 158.6 K pairs/s, 72 chunks 159.9 K, 85 chunks 156.4 K.
-    const int align = tn_pp ? 64 : L.p[0].elt ? 32 : 16;      // K tile of the kernel (bf16 storage: 32 rows, ping-pong tile: 64)
-    if (tn_pp) {
-      // one workgroup per CU: as many K chunks as fill ONE round of 256 workgroups when that occupies >= 85 % of them (h = 768: a
-      // cell's 7 outputs = 63 tiles x 4 chunks = 252), else two rounds; chunks of at least 1024 rows.  The XCD rule does not apply:
-      // the kernel deals its items to the XCDs in runs.
-      const int tiles = L.nprob * L.m_tiles * L.n_tiles;
-      const int ks1 = 256 / tiles > 0 ? 256 / tiles : 1, ks2 = 512 / tiles > 0 ? 512 / tiles : 1;
-      const double e1 = tiles * ks1 / 256.0, e2 = tiles * ks2 / 512.0;
-      ks = (e1 >= 0.85 || e1 >= e2) ? ks1 : ks2;
-      const int kmax = k_total / 1024 > 1 ? k_total / 1024 : 1;
-      if (ks > kmax) ks = kmax;
-      // (the partial tiles must fit the workspace: fewer chunks otherwise)
-      size_t out_bytes = 0;
-      for (int i = 0; i < L.nprob; ++i) out_bytes += ((size_t)L.p[i].M * L.p[i].N + (cs_out[i] ? (size_t)L.p[i].M : 0)) * sizeof(float);
-      while (ks > 1 && (size_t)ks * out_bytes > g_ws_bytes) --ks;
-    } else
-    if (ks >= 12) ks = ((ks + 4) / 8) * 8;
-    int chunk = (k_total + ks - 1) / ks;
-    chunk = ((chunk + align - 1) / align) * align;
-    L.kchunk = chunk;
-    L.ksplit = (k_total + chunk - 1) / chunk;
-    if (tn_pp) L.per = (L.nprob * L.m_tiles * L.n_tiles * L.ksplit + 7) / 8;
-    if (!tn_pp && L.ksplit >= 12 && L.ksplit % 8 != 0) {      // rounding the chunk up dropped a chunk or two: stretch the chunks to the multiple of 8 below
-      const int k8 = (L.ksplit / 8) * 8;
-      chunk = (((k_total + k8 - 1) / k8 + align - 1) / align) * align;
-      if ((k_total + chunk - 1) / chunk % 8 == 0) { L.kchunk = chunk; L.ksplit = (k_total + chunk - 1) / chunk; }
-    }
-    // partial tiles -> workspace when it is big enough and every output is float4-shaped
-    size_t need = 0;
-    bool want_cs0 = false;
-    for (int i = 0; i < L.nprob; ++i) want_cs0 = want_cs0 || cs_out[i] != nullptr;
-    // (a single chunk also goes through the workspace when the ping-pong kernel runs it -- it only writes partial tiles -- or when
-    //  bf16 operands want their bias gradient: that rides in the fused kernels' workspace path only)
-    bool ws_ok = g_ws != nullptr && (L.ksplit > 1 || tn_pp || (want_cs0 && L.p[0].elt));
-    bool any_cs = false;
-    for (int i = 0; i < L.nprob && ws_ok; ++i) {
-      if (L.p[i].N % 4) ws_ok = false;
-      need += (size_t)L.ksplit * L.p[i].M * L.p[i].N * sizeof(float);
-      if (cs_out[i]) { need += (size_t)L.ksplit * L.p[i].M * sizeof(float); any_cs = true; }
-    }
-    bool want_cs = false;
-    for (int i = 0; i < L.nprob; ++i) want_cs = want_cs || cs_out[i] != nullptr;
-    if (any_cs && !(ws_ok && need <= g_ws_bytes && fast_ok(L, true) && (g_gemm_mode != 1 || L.p[0].elt))) any_cs = false;
-    if (want_cs && !any_cs) {
-      // this launch cannot carry its column sums (no workspace, generic kernel): fp32 operands get them from the streaming
-      // kernel right here, so that a Batch whose problems span several launches (h = 768: 21 column-block problems) never ends
-      // up with some bias gradients fused and others missing; bf16 operands have no such kernel -- the caller is told
-      for (int i = 0; i < L.nprob; ++i) {
-        if (!cs_out[i]) continue;
-        const Seg& sg = L.p[i].seg[0];
-        if (L.p[i].elt || sg.lda != L.p[i].M) { colsum_missed = true; continue; }
-        if (launch_colsum3(sg.A, nullptr, nullptr, cs_out[i], nullptr, nullptr, sg.K, L.p[i].M, s, cs_out2[i], nullptr, nullptr)) colsum_missed = true;
-        else colsum_fused = true;
-      }
-    }
-    if (ws_ok && need <= g_ws_bytes) {
-      ReduceArgs R;
-      R.n = L.nprob;
-      float* w = g_ws;
-      int max_elems = 0;
-      for (int i = 0; i < L.nprob; ++i) {
-        Problem& q = L.p[i];
-        R.it[i] = ReduceItem{w, q.C, q.M, q.N, q.ldc, L.ksplit, (long long)q.M * q.N};
-        q.C = w; q.ldc = q.N; q.epi = EPI_STORE; q.accumulate = 0; q.split_stride = (long long)q.M * q.N;
-        w += (size_t)L.ksplit * q.M * q.N;
-        if (q.M * (q.N / 4) > max_elems) max_elems = q.M * (q.N / 4);
-      }
-      ReduceArgs RC;          // bias-gradient partials [ksplit][M] behind the tiles, summed into one or two outputs
-      RC.n = 0;
-      int max_cs = 0;
-      for (int i = 0; i < L.nprob && any_cs; ++i) {
-        Problem& q = L.p[i];
-        if (!cs_out[i]) continue;
-        q.colsum = w; q.colsum_stride = q.M;
-        RC.it[RC.n++] = ReduceItem{w, cs_out[i], 1, q.M, q.M, L.ksplit, (long long)q.M};
-        if (cs_out2[i] && RC.n < GH_MAX_PROBLEMS) RC.it[RC.n++] = ReduceItem{w, cs_out2[i], 1, q.M, q.M, L.ksplit, (long long)q.M};
-        w += (size_t)L.ksplit * q.M;
-        if (q.M / 4 > max_cs) max_cs = q.M / 4;
-      }
-      hipError_t e = launch_any();
-      if (e != hipSuccess) err = e;
-      // one reduce launch: the bias-gradient partials ride behind the tiles (their workgroups beyond the first exit at once)
-      for (int i = 0; i < RC.n; ++i) R.it[R.n++] = RC.it[i];
-      if (max_cs > max_elems) max_elems = max_cs;
-      hipLaunchKernelGGL(reduce_partials_kernel, dim3((max_elems + 255) / 256, R.n), dim3(256), 0, s, R);
-      if (RC.n > 0) colsum_fused = true;
-      e = hipGetLastError();
-      if (e != hipSuccess) err = e;
-      reset();
-      return;
-    }
-  }
-  if (tn && tn_pp) { err = hipErrorInvalidValue; reset(); return; }      // (the ping-pong kernel writes partial tiles only: no workspace, no launch)
-  if (!tn && nt_split_plan()) return;
-  hipError_t e = launch_any();
-  if (e != hipSuccess) err = e;
-  reset();
+hipError_t launch_reduce_partials(const ReduceArgs& R, int max_elems, hipStream_t s) {
+  hipLaunchKernelGGL(reduce_partials_kernel, dim3((max_elems + 255) / 256, R.n), dim3(256), 0, s, R);
+  return hipGetLastError();
 }
-
-hipError_t Batch::launch_any() {
-  if (tn && tn_pp) return launch_tn_pp(L, s);
-  if (narrow && !tn && L.ksplit == 1 && !L.p[0].elt) return launch_cfg<2, 2, 5>(L, tn, s);
-  if (big && !tn && L.ksplit == 1 && !L.p[0].elt) {
-    // Occupancy-aware tile choice.  The chip holds 768 workgroups of either configuration (3 per CU); a grid of 64-row
-    // tiles that ends in a thinly filled last round (e.g. 976 workgroups = 1.27 rounds, the node-compact single-problem
-    // launches) runs faster on 32-row tiles (1937 workgroups = 2.52 rounds): measured 83 vs 78 TF at K = 300.
-    const double r = (double)L.m_tiles * L.nprob / 768.0;
-    const double frac = r - (double)(long long)r;
-    if (g_gemm_mode != 1 && r < 3.0 && frac > 0.02 && frac < 0.45) {
-      int mt = 0;
-      for (int i = 0; i < L.nprob; ++i) { const int t = (L.p[i].M + 31) / 32; if (t > mt) mt = t; }
-      L.m_tiles = mt;
-      return launch_cfg<1, 4, 5>(L, tn, s);
-    }
-  }
-  if (wide256) {
-    // the ping-pong loop's preconditions (gemm_nt_pp.hip.h): whole 64-deep K tiles, no K split, no dropout inside the K loop
-    bool ok = L.ksplit == 1;
-    for (int i = 0; i < L.nprob; ++i) {
-      if (L.p[i].drop_mode == 1) ok = false;
-      for (int j = 0; j < L.p[i].nseg; ++j) if (L.p[i].seg[j].K % 64) ok = false;
-    }
-    if (ok) return launch_cfg<2, 4, 4, 8>(L, tn, s);
-    int mt = 0;
-    for (int i = 0; i < L.nprob; ++i) { const int t = (L.p[i].M + 127) / 128; if (t > mt) mt = t; }
-    L.m_tiles = mt;
-    return launch_cfg<2, 2, 8, 4>(L, tn, s);
-  }
-  if (wide) return launch_cfg<2, 2, 8, 4>(L, tn, s);
-  return big ? launch_cfg<2, 2, 10>(L, tn, s) : launch_cfg<1, 4, 5>(L, tn, s);
-}
-
-// Few-row NT GEMMs (evidence level, head): too few row tiles to fill 256 CUs, so split K across
-// workgroups, keep the partial tiles in the workspace and finish with nt_finish_kernel.
-bool Batch::nt_split_plan() {
-  const int blocks = L.m_tiles * L.nprob;
-  constexpr int max_blocks = 96;
-  if (g_ws == nullptr || blocks >= max_blocks || !fast_ok(L, false)) return false;
-  int tmax = 0;          // K tiles over the concatenated segments (every problem of a launch is split alike)
-  for (int i = 0; i < L.nprob; ++i) {
-    const Problem& q = L.p[i];
-    if (q.epi == EPI_ATOMIC || q.epi == EPI_GATE_PRE || q.drop_mode != 0 || (q.epi == EPI_TANH_H && q.w2) || q.seg0_rows > 0 || q.elt) return false;   // (fp32 problems only)
-    int t = 0;
-    for (int j = 0; j < q.nseg; ++j) t += (q.seg[j].K + 15) / 16;
-    if (i > 0 && t != tmax) return false;
-    tmax = t;
-  }
-  int ks = tmax / 4;
-  // workgroups wanted: one per CU -- two for long contractions (>= 128 K tiles, e.g. the evidence-level attention at h = 768:
-  // K = 6272), where a split-K workgroup is MFMA-bound rather than latency-bound (A/B configs[4] bf16: 256 / 512 / 768 =
-  // 107.7 / 108.7 / 108.1 K pairs/s; headline and Snopes-count steps unchanged at any of them)
-  const int tgt = tmax >= 128 ? 512 : 256;
-  const int want = (tgt + blocks - 1) / blocks;
-  if (ks > want) ks = want;
-  if (ks < 2) return false;
-  const int ct = (tmax + ks - 1) / ks;     // tiles per chunk
-  ks = (tmax + ct - 1) / ct;
-  if (ks < 2) return false;
-  size_t need = 0;
-  for (int i = 0; i < L.nprob; ++i) need += (size_t)ks * L.p[i].M * L.p[i].N * sizeof(float);
-  if (need > g_ws_bytes) return false;
-  FinishArgs F;
-  F.n = L.nprob;
-  float* w = g_ws;
-  int max_m = 0;
-  for (int i = 0; i < L.nprob; ++i) {
-    Problem& q = L.p[i];
-    F.it[i] = FinishItem{w, (long long)q.M * q.N, ks, q.M, q.N, q.epi, q.accumulate, q.ldc,
-                         q.C, q.bias, q.bias2, q.out1, q.in0, q.in1, q.u, q.w2, q.e, q.ldu, q.R, q.heads, q.rowg};
-    q.C = w; q.ldc = q.N; q.epi = EPI_STORE; q.accumulate = 0; q.bias = nullptr; q.bias2 = nullptr;
-    q.split_stride = (long long)q.M * q.N;
-    w += (size_t)ks * q.M * q.N;
-    if (q.M > max_m) max_m = q.M;
-  }
-  L.ksplit = ks;
-  L.kchunk = ct * 16;
-  hipError_t e = launch_any();
-  if (e != hipSuccess) err = e;
-  // many partials over few rows: a workgroup per row (the four waves share the partials); otherwise a wave per row
-  F.split = (ks >= 16 && max_m <= 8192) ? 1 : 0;      // (ks = 9, M = 960 -- the claim cell, the evidence-level attention -- measured equal or slower split)
-  hipLaunchKernelGGL(nt_finish_kernel, dim3(F.split ? max_m : (max_m + 3) / 4, F.n), dim3(256), 0, s, F);
-  split_done = true;
-  e = hipGetLastError();
-  if (e != hipSuccess) err = e;
-  reset();
-  return true;
+hipError_t launch_nt_finish(const FinishArgs& F, int grid_x, hipStream_t s) {
+  hipLaunchKernelGGL(nt_finish_kernel, dim3(grid_x, F.n), dim3(256), 0, s, F);
+  return hipGetLastError();
 }
 
 // the layers' two direct uses of this file's kernels (gemm_batch.h)

@@ -1,5 +1,5 @@
 """Every dispatch path of the plain linear GEMMs (gh_linear_fwd / gh_linear_bwd of csrc/dense_ops.hip: the host planner `Batch` of
-csrc/gemm_ops.hip with the NT, TN and generic MFMA kernels, the split-K finish and reduce kernels, the tiny-width kernels
+csrc/gemm_batch.hip with the NT, TN and generic MFMA kernels, the split-K finish and reduce kernels, the tiny-width kernels
 and the column sums of csrc/stream_ops.hip) against float64 on the CPU, and gh_transpose / gh_transpose_batch /
 gh_weights_refresh bit for bit.
 
@@ -14,8 +14,9 @@ which kernel family ran (fast / generic) and how many launches a call took; with
 separately prepared buffers must agree bit for bit wherever no floating-point atomic orders the sum.
 
 Shapes are (m, k, n) of y[m][n] = x[m][k] w[n][k]^T + b.  The backward of a shape runs dX as an NT product with
-(M, N, K) = (m, k, n) and dW as a TN product with output [n][k] contracted over m.  The plan named next to a shape was
-derived from `Batch` (add / flush / nt_split_plan / launch_any) and launch_colsum3 by reading them.  What a run itself
+(M, N, K) = (m, k, n) and dW as a TN product with output [n][k] contracted over m.  The plan named next to a shape is
+the planner's (csrc/gemm_plan.h): tools/gemm_plan_sweep.cpp asserts each of them on the CPU (tests/test_gemm_plan_cpu.py);
+launch_colsum3's were derived by reading it.  What a run itself
 verifies of a plan: the kernel family and the launch count (path counters), and whether partial tiles and column-sum
 partials were written to the workspace (its first float, and the first float of its column-sum tail, are no longer the
 NaN they were filled with), which tells split from unsplit NT launches, the workspace from the atomic TN path and the
