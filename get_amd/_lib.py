@@ -119,6 +119,8 @@ SIGNATURES = {
     "gh_window_mean_fwd": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P],
     "gh_window_mean_bwd": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P],
     "gh_match_hist": [_P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "gh_embed_fwd": [_P, _P, _P, _I, _I, _I, _P],
+    "gh_embed_bwd": [_P, _L, _P, _P, _I, _I, _I, _I, _P, _P, _L, _P],
     # library-owned RCCL communicator (csrc/comm_ops.hip; librccl is dlopen'ed on first use)
     "gh_comm_unique_id": [_P],
     "gh_comm_init": [_P, _I, _I, _P],

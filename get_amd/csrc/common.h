@@ -112,7 +112,8 @@ int launch_colsum3(const float* a, const float* b, const float* c, float* oa, fl
                    hipStream_t s, float* oa2 = nullptr, float* ob2 = nullptr, float* oc2 = nullptr);
 int launch_colsum(const float* a, float* oa, int m, int h, hipStream_t s);
 int launch_gather_rows(const float* table, const int32_t* ids, float* dst, int m, int d, hipStream_t s,
-                       float drop_p = 0.f, unsigned drop_seed = 0, int bf16 = 0);   // bf16: table and dst hold bf16
+                       float drop_p = 0.f, unsigned drop_seed = 0, int bf16 = 0,    // bf16: table and dst hold bf16
+                       int table_rows = 0);      // > 0 (fp32 only): ids are clamped into [0, table_rows) before they are used
 int launch_tiny_linear_fwd(const float* x, const float* w, const float* bias, float* y, int m, int k, int n, hipStream_t s);
 int launch_tiny_linear_bwd(const float* x, const float* w, const float* g, float* dx, float* dw, float* db, int m, int k, int n,
                            hipStream_t s);

@@ -51,7 +51,7 @@ void prof_end(int tag, double work, hipStream_t s) {
 }
 
 // Device counters of clamped out-of-range inputs (include/get_hip.h gh_clamp_events): four unsigned ints per device, allocated
-// on first use, handed to the kernels that clamp (cross_entropy: [0], left_assemble: [1], evd_assemble: [2]).
+// on first use, handed to the kernels that clamp (cross_entropy: [0], left_assemble: [1], evd_assemble: [2], embed_bwd: [3]).
 static std::mutex g_clamp_mu;
 static std::unordered_map<int, unsigned int*> g_clamp_buf;
 unsigned int* clamp_counter() {

@@ -203,7 +203,7 @@ int launch_colsum(const float* a, float* oa, int m, int h, hipStream_t s) {
 // dst[r][:] = dropout(table[ids ? ids[r] : r][:]) -- the operand of the dW_proj GEMM, with the forward's mask
 __global__ void __launch_bounds__(256)
 gather_rows_kernel(const float* __restrict__ table, const int32_t* __restrict__ ids, float* __restrict__ dst, int m,
-                   int d, unsigned drop_thresh, float drop_scale, unsigned drop_seed) {
+                   int d, unsigned drop_thresh, float drop_scale, unsigned drop_seed, int table_rows) {
   const int per = (d + 3) / 4;
   if (d % 4 == 0 && ((reinterpret_cast<uintptr_t>(table) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) {
     // four independent id -> row chains per thread and trip (as gather_rows_bf16_kernel: one chain at a time left the kernel parked
@@ -219,6 +219,9 @@ gather_rows_kernel(const float* __restrict__ table, const int32_t* __restrict__ 
       }
 #pragma unroll
       for (int k = 0; k < 4; ++k) src[k] = ids ? ids[r[k]] : r[k];
+      if (table_rows)      // (gh_embed_fwd: ids nobody has checked are clamped into the table)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) src[k] = min(max(src[k], 0), table_rows - 1);
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[k] = *reinterpret_cast<const float4*>(table + (size_t)src[k] * d + c[k]);
 #pragma unroll
@@ -233,7 +236,9 @@ gather_rows_kernel(const float* __restrict__ table, const int32_t* __restrict__ 
   }
   for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < (size_t)m * per; it += (size_t)gridDim.x * blockDim.x) {
     const int r = (int)(it / per), c = 4 * (int)(it % per);
-    const float* s = table + (size_t)(ids ? ids[r] : r) * d + c;
+    int src = ids ? ids[r] : r;
+    if (table_rows) src = min(max(src, 0), table_rows - 1);
+    const float* s = table + (size_t)src * d + c;
     float* o = dst + (size_t)r * d + c;
     if (d % 4 == 0) {
       float4 v = *reinterpret_cast<const float4*>(s);
@@ -294,11 +299,12 @@ gather_rows_bf16_kernel(const unsigned short* __restrict__ table, const int32_t*
 }
 
 int launch_gather_rows(const float* table, const int32_t* ids, float* dst, int m, int d, hipStream_t s, float drop_p,
-                       unsigned drop_seed, int bf16) {
+                       unsigned drop_seed, int bf16, int table_rows) {
   if (m <= 0) return 0;
   GH_REQUIRE(drop_p <= 0.f || (long long)m * (long long)d < (1LL << 32), "gather_rows: %d rows x %d columns exceed the dropout mask's 32-bit element index", m, d);
   if (bf16) {
     GH_REQUIRE(d % 4 == 0, "gather_rows: the bf16 variant needs d %% 4 == 0");
+    GH_REQUIRE(table_rows == 0, "gather_rows: the bf16 variant does not clamp ids");
     const size_t n = (size_t)m * (d / 4);
     const double th = (double)drop_p * 4294967296.0;
     const unsigned thresh = drop_p > 0.f ? (th >= 4294967295.0 ? 4294967295u : (unsigned)th) : 0u;
@@ -311,7 +317,7 @@ int launch_gather_rows(const float* table, const int32_t* ids, float* dst, int m
   const double th = (double)drop_p * 4294967296.0;
   const unsigned thresh = drop_p > 0.f ? (th >= 4294967295.0 ? 4294967295u : (unsigned)th) : 0u;
   hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096)), dim3(256), 0, s,
-                     table, ids, dst, m, d, thresh, 1.0f / (1.0f - drop_p), drop_seed);
+                     table, ids, dst, m, d, thresh, 1.0f / (1.0f - drop_p), drop_seed, table_rows);
   GH_LAUNCH_CHECK();
   return 0;
 }

@@ -69,6 +69,29 @@ class Linear(nn.Module):
         return ops.linear(x, self.linear.weight, self.linear.bias)
 
 
+# ------------------------------------------------------------------ Models/base_model.py:144-162 (the layers it builds)
+class Embedding(nn.Embedding):
+    """torch.nn.Embedding whose GPU lookup and table gradient run in the library (ops.embedding): same constructor and
+    ``from_pretrained``, the single state_dict key ``weight``, ``padding_idx`` honoured (its row receives no gradient).  The
+    gradient of a trainable table is a row sum in a fixed order -- two backward passes give the same bits, which
+    index_add_ / ATen's atomics do not promise -- and lands straight in ``weight.grad`` under a dist.FlatTrainer.
+    ``max_norm``, ``scale_grad_by_freq`` and ``sparse=True`` are refused at construction: the reference sets none of them.
+    A CPU weight takes torch's own forward (the models are constructed, loaded and inspected on the CPU)."""
+
+    def __init__(self, num_embeddings, embedding_dim, padding_idx=None, max_norm=None, norm_type=2.0, scale_grad_by_freq=False,
+                 sparse=False, **kwargs):
+        if max_norm is not None or scale_grad_by_freq or sparse:
+            raise ValueError("get_amd.modules.Embedding: max_norm, scale_grad_by_freq and sparse=True are not supported "
+                             "(torch.nn.Embedding has them)")
+        super().__init__(num_embeddings, embedding_dim, padding_idx=padding_idx, max_norm=None, norm_type=norm_type,
+                         scale_grad_by_freq=False, sparse=False, **kwargs)
+
+    def forward(self, input):
+        if not self.weight.is_cuda:
+            return super().forward(input)
+        return ops.embedding(self.weight, input, self.padding_idx)
+
+
 # ------------------------------------------------------------------ Models/BiDAF/wrapper.py:174-208
 class GGNN(nn.Module):
     def __init__(self, in_features, out_features, dropout=0.2):
@@ -871,14 +894,14 @@ class Graph_basedSemantiStructure(nn.Module):
         if isinstance(_params["embedding"], np.ndarray):
             _params["embedding_input_dim"] = _params["embedding"].shape[0]
             _params["embedding_output_dim"] = _params["embedding"].shape[1]
-            return nn.Embedding.from_pretrained(embeddings=torch.Tensor(_params["embedding"]),
-                                                freeze=_params["embedding_freeze"])
-        return nn.Embedding(num_embeddings=_params["embedding_input_dim"],
-                            embedding_dim=_params["embedding_output_dim"])
+            return Embedding.from_pretrained(embeddings=torch.Tensor(_params["embedding"]),
+                                             freeze=_params["embedding_freeze"])
+        return Embedding(num_embeddings=_params["embedding_input_dim"],
+                         embedding_dim=_params["embedding_output_dim"])
 
     @staticmethod
     def _make_entity_embedding_layer(matrix: np.ndarray, freeze: bool) -> nn.Module:
-        return nn.Embedding.from_pretrained(embeddings=torch.Tensor(matrix), freeze=freeze)
+        return Embedding.from_pretrained(embeddings=torch.Tensor(matrix), freeze=freeze)
 
     # -- forward (:76-125)
     def forward(self, query: torch.Tensor, document: torch.Tensor, verbose=False, **kargs):

@@ -10,6 +10,7 @@ import torch
 from .. import _lib
 from .._lib import call, ptr, stream
 from ._util import _f32
+from .embed import table_grad
 from .weights import _direct, bf16_twins, derived, transposed
 
 
@@ -234,6 +235,7 @@ class _GGNNCell(torch.autograd.Function):
             ctx.adj, ctx.ids, ctx.dims, ctx.plan, ctx.rows = adj, ids, (n, r, din, h), plan, (m, mb)
             ctx.drop = (float(drop_p), int(drop_seed))
             ctx.params = (w_p, w_z0, b_z0, w_z1, b_z1, w_r0, b_r0, w_r1, b_r1, w_h0, b_h0, w_h1, b_h1)
+            ctx.table = x if ids is not None else None      # (what is saved below is its bf16 twin)
             ctx.save_for_backward(xb, bufb, *wts_b)
             ctx.x_needs_grad = ctx.needs_input_grad[0]
             ctx.x_shape = tuple(x.shape)
@@ -257,6 +259,7 @@ class _GGNNCell(torch.autograd.Function):
         ctx.adj, ctx.ids, ctx.dims, ctx.plan, ctx.rows = adj, ids, (n, r, din, h), plan, (m, mb)
         ctx.drop = (float(drop_p), int(drop_seed))
         ctx.params = (w_p, w_z0, b_z0, w_z1, b_z1, w_r0, b_r0, w_r1, b_r1, w_h0, b_h0, w_h1, b_h1)
+        ctx.table = x if ids is not None else None
         ctx.save_for_backward(x, buf, *wts)
         ctx.x_needs_grad = ctx.needs_input_grad[0]
         res = out.view(n, r, h) if plan is None else out
@@ -306,10 +309,8 @@ class _GGNNCell(torch.autograd.Function):
              ptr(dhp), ptr(dzp), ptr(drp), ptr(dxp), ptr(da),
              ptr(dx), *[ptr(t) for t in gw], *[ptr(t) for t in gb], ctx.drop[0], ctx.drop[1], stream())
         if want_dx:
-            if ids is not None:      # trainable embedding table: scatter the row gradients
-                demb = torch.zeros(x.shape, device=dev, dtype=torch.float32)
-                demb.index_add_(0, ids[:m].long(), dx)
-                dx = demb
+            if ids is not None:      # trainable embedding table: the row gradients summed by id in a fixed order
+                dx = table_grad(ctx.table, dx, ids[:m])      # (None: added straight into the table's .grad)
             else:
                 dx = dx.view(ctx.x_shape if bf else x.shape)
         if direct:

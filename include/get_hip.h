@@ -613,7 +613,8 @@ int gh_evd_assemble_bwd(const float* g, const int32_t* offsets, const void* sour
                         int xa, int ds, float* d_avg, float* d_table, gh_stream_t stream);
 /* Out-of-range inputs the kernels clamped for memory safety where the reference would have RAISED (nn.Embedding /
  * nn.CrossEntropyLoss index errors): out_host[0] = labels outside [0, c) seen by gh_cross_entropy, [1] = claim-source ids,
- * [2] = article-source ids outside their table (other than the -1 padding id), [3] = reserved; counted on the CURRENT device since
+ * [2] = article-source ids outside their table (other than the -1 padding id), [3] = ids outside [0, vocab) among the rows handed
+ * to gh_embed_bwd (they contribute nothing there; the padding id is not counted); counted on the CURRENT device since
  * the last reset.  Synchronises the device.  A training loop checks it once per epoch (or per step in debug runs): a non-zero
  * count means corrupt input data was trained on as if it were class / row 0 or the last one. */
 int gh_clamp_events(int64_t* out4_host, int reset);
@@ -889,6 +890,34 @@ int gh_window_mean_bwd(const float* g, int ldg, const float* mask, int bn, int l
  *   through an id, so the call synchronises the stream).  No backward.  Limits: lq, ld <= 1024, d <= 2048, bins <= 256. */
 int gh_match_hist(const float* table, int ldt, const float* inv_norm, int v, int d, const int32_t* ids_left, const int32_t* ids_right,
                   const int32_t* len_right, int bn, int lq, int ld, int bins, int mode, float* out, int32_t* flag, gh_stream_t stream);
+
+/* ---- embedding table: torch.nn.Embedding as Models/base_model.py:144-162 builds it (_make_default_embedding_layer with
+ *      embedding_freeze, _make_entity_embedding_layer) and graph_based_semantic_structure.py:100,113,150,169 and
+ *      Models/BiDAF/bidaf_model.py:128-129 look it up ----
+ * Forward (ATen's embedding): out [m][d] = table[ids[i]] for a table [vocab][d]; any d >= 1, float4 copies where d % 4 == 0 and
+ * both row sets are 16-byte aligned.  An id outside [0, vocab) is clamped into the table for memory safety (nn.Embedding
+ * raises); the backward counts it. */
+int gh_embed_fwd(const float* table, const int32_t* ids, float* out, int m, int d, int vocab, gh_stream_t stream);
+/* Backward (ATen's embedding_dense_backward, and the zeros + index_add_ of a table gradient): dtable[t][:] += the sum of the
+ * rows dx[i][:] with ids[i] == t, for dx [m][d] with the leading dimension ldx >= d (floats) and dtable [vocab][d], addressed in
+ * 64 bits.  It ACCUMULATES; a row of dtable that no id names is neither read nor written.
+ *   sorted_ids [m], perm [m] int32: the ids in ascending order and, for every sorted position, its row of dx; equal ids in
+ *   ascending row order (a stable sort of the ids gives both).
+ *   padding_idx: rows with that id contribute nothing (-1 = none).  So do rows whose id is outside [0, vocab); those are counted
+ *   in slot [3] of gh_clamp_events (the padding id is not), and nothing is ever written through them.
+ *   workspace: 2 * ceil(m / GH_EMBED_CHUNK) * d floats of scratch (workspace_floats says how many there are); nothing allocates.
+ * The order of the additions is part of the contract, so that a host restatement (tests/embed_ref.py) gives the same bits and
+ * two calls on the same inputs give the same table on any grid and device:
+ *   1. the sorted positions 0 .. m-1 are cut into chunks of GH_EMBED_CHUNK;
+ *   2. inside a chunk the rows of a run of equal ids are added one after the other in ascending sorted position, starting from
+ *      the run's first row: the chunk's partial p_c of that id;
+ *   3. a run that spans the chunks c_1 < .. < c_k is combined as ((p_1 + p_2) + ..) + p_k;
+ *   4. the result is added to the table row once: dtable[t] = dtable[t] + (..).
+ * These are fp32 additions in round-to-nearest, no FMA.  One writer per element of dtable and no floating-point atomics.
+ * m == 0 is a no-op.  Calls that accumulate into one dtable must be ordered by their streams. */
+#define GH_EMBED_CHUNK 128
+int gh_embed_bwd(const float* dx, long long ldx, const int32_t* sorted_ids, const int32_t* perm, int m, int d, int vocab,
+                 int padding_idx, float* dtable, float* workspace, long long workspace_floats, gh_stream_t stream);
 
 /* Everything the forward / backward need that is DERIVED from weight matrices, for n matrices in one launch (after the
  * optimiser step): dst_t[i] = src[i]^T as fp32 [cols][rows] (the backward's dX operands), and -- bf16 storage mode, any of the
