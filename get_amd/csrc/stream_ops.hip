@@ -240,16 +240,12 @@ gather_rows_kernel(const float* __restrict__ table, const int32_t* __restrict__ 
     if (table_rows) src = min(max(src, 0), table_rows - 1);
     const float* s = table + (size_t)src * d + c;
     float* o = dst + (size_t)r * d + c;
-    if (d % 4 == 0) {
-      float4 v = *reinterpret_cast<const float4*>(s);
-      if (drop_thresh) v = drop4(v, drop_seed, (unsigned)r * (unsigned)d + (unsigned)c, drop_thresh, drop_scale);
-      *reinterpret_cast<float4*>(o) = v;
-    } else {
-      for (int k = 0; k < 4 && c + k < d; ++k) {
-        float v = s[k];
-        if (drop_thresh) v = drop_hash(drop_seed, (unsigned)r * (unsigned)d + (unsigned)(c + k)) >= drop_thresh ? v * drop_scale : 0.f;
-        o[k] = v;
-      }
+    // rows that are no multiple of 4 floats wide, or a base that is not 16-byte aligned: single floats only (a float4 access
+    // needs both, and this loop is entered exactly when one of them fails)
+    for (int k = 0; k < 4 && c + k < d; ++k) {
+      float v = s[k];
+      if (drop_thresh) v = drop_hash(drop_seed, (unsigned)r * (unsigned)d + (unsigned)(c + k)) >= drop_thresh ? v * drop_scale : 0.f;
+      o[k] = v;
     }
   }
 }

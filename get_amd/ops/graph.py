@@ -363,7 +363,7 @@ def dropout_mask_reference(seed: int, rows: int, cols: int, p: float):
     x ^= x >> np.uint64(13)
     x = (x * np.uint64(0xC2B2AE35)) & np.uint64(0xFFFFFFFF)
     x ^= x >> np.uint64(16)
-    t = p * 4294967296.0
+    t = float(np.float32(p)) * 4294967296.0      # the C-ABI takes p as a float: (double)drop_p * 2^32, as the launchers form it
     thresh = np.uint64(4294967295 if t >= 4294967295.0 else int(t))
     return x >= thresh
 

@@ -162,7 +162,12 @@ int gh_ggnn_cell_fwd(const uint64_t* bits, const float* dinv, const float* vals,
  * parameters' own .grad buffers).  b?0 and b?1 share one gradient: db_z1/db_r1/db_h1 (NULL ok) receive
  * the same column sums, so both biases' .grad can be fed without a copy.
  * goff != NULL: node-compact layout, the backward runs on the m_real real-node rows only (padding rows get and give
- * no gradient; dx rows beyond m_real are not written). */
+ * no gradient; dx rows beyond m_real are not written).
+ * Alignment (both fp32 entries): every tensor needs its element's alignment only (4 bytes).  16-byte aligned tensors whose
+ * rows are a multiple of 4 floats take the vector kernels; anything else -- a width that is no multiple of 4, or a base
+ * address off a 16-byte boundary, x / the table behind ids included -- takes kernels that touch single floats only (the
+ * generic GEMM, gate_bwd_pre's scalar kernel, gather_rows' single-float loop), with the same results.  The bf16 entries
+ * require 16-byte aligned tensors. */
 int gh_ggnn_cell_bwd(const uint64_t* bits, const float* dinv, const float* vals, const uint64_t* keep,
                      const int32_t* goff, int m_real,
                      const float* x, const int32_t* ids, int n, int r, int din, int h,

@@ -1,7 +1,9 @@
 """The GEMM planner (csrc/gemm_plan.h: tile choice, fast-path rule, split-K plans, workspace layout, kernel configuration, grid) on
 the CPU: tools/gemm_plan_sweep.cpp is built with the host compiler under ASan / UBSan and run as a stand-alone child process.  It
 walks the planner over shape classes, checks the invariants the kernels rely on, asserts the plans the project relies on (those
-named in tests/test_gpu_gemm_paths.py and the bench step's) exactly, and exits non-zero on any violation."""
+named in tests/test_gpu_gemm_paths.py, the bench step's, and every launch of every case of tests/test_gpu_cell_paths.py: tile,
+split with chunk count and finish shape, fast or generic, workspace or atomic, column sums fused or separate) exactly, and exits
+non-zero on any violation."""
 import pathlib
 import re
 import subprocess

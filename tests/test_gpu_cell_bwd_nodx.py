@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.util import cell_backward_f64
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 N, R, COUNTS, VOCAB = 3, 20, (20, 7, 1), 128
@@ -84,36 +86,7 @@ def _params(num, grads=True):
     return w, b, order
 
 
-# ----------------------------------------------------------------------------- float64 reference, written out
-def cell_backward_f64(adj, x, g, w, b):
-    """adj (N,R,R), x (N,R,din) the masked input rows, g (N,R,h): every gradient of the cell, by hand, in float64."""
-    sig = torch.sigmoid
-    W = {k: v.double() for k, v in w.items()}
-    B = {k: v.double() for k, v in b.items()}
-    xp = x @ W["p"].t()
-    a = adj @ xp
-    z = sig(a @ W["z0"].t() + B["z0"] + xp @ W["z1"].t() + B["z1"])
-    r = sig(a @ W["r0"].t() + B["r0"] + xp @ W["r1"].t() + B["r1"])
-    rx = r * xp
-    hh = torch.tanh(a @ W["h0"].t() + B["h0"] + rx @ W["h1"].t() + B["h1"])
-    dhp = g * z * (1 - hh * hh)
-    dzp = g * (hh - xp) * z * (1 - z)
-    dxp = g * (1 - z)
-    da = dhp @ W["h0"]
-    drx = dhp @ W["h1"]
-    drp = drx * xp * r * (1 - r)
-    dxp = dxp + drx * r
-    da = da + dzp @ W["z0"] + drp @ W["r0"]
-    dxp = dxp + dzp @ W["z1"] + drp @ W["r1"]
-    dxp = dxp + adj.transpose(1, 2) @ da
-    tn = lambda p, q: torch.einsum("nri,nrj->ij", p, q)
-    dw = {"p": tn(dxp, x), "z0": tn(dzp, a), "z1": tn(dzp, xp), "r0": tn(drp, a), "r1": tn(drp, xp), "h0": tn(dhp, a),
-          "h1": tn(dhp, rx)}
-    col = lambda p: p.sum((0, 1))
-    db = {"z0": col(dzp), "z1": col(dzp), "r0": col(drp), "r1": col(drp), "h0": col(dhp), "h1": col(dhp)}
-    return dw, db, dxp @ W["p"]
-
-
+# ----------------------------------------------------------------------------- float64 reference (tests/util.py)
 def _reference(num, adj, drop_p, seed, compact, din, h):
     """Gradients of the call on the padded (compact = False) or the node-compact layout; the stateless dropout mask is
     indexed by the call's own row."""

@@ -25,8 +25,9 @@ for those the evidence is a mutation check on a scratch copy of the library (one
 that label fail), listed in the commit that added this file.
 
 Out of scope here, because gh_linear_* cannot reach them: the 64 x 160 narrow tile, the fused gate and attention
-epilogues, dropout inside the loaders, two-segment problems and the bf16 storage tiles (they stay with the cell and
-attention tests); GEMM modes 1 (bf16 operands) and 2 keep their own tests in tests/test_gpu_ops.py."""
+epilogues, dropout inside the loaders, two-segment problems and the bf16 storage tiles: tests/test_gpu_cell_paths.py reaches
+them through the GGNN cell entries, at this file's bound and with this file's fences (the attention epilogues stay with the
+attention path tests); GEMM modes 1 (bf16 operands) and 2 keep their own tests in tests/test_gpu_ops.py."""
 import ctypes
 import functools
 import math

@@ -484,6 +484,60 @@ def g_depad(counts, n_max, r, ids, adj):
     return out
 
 
+# ----------------------------------------------------------------------------- GGNN cell restatement (float64, tests only)
+# What gh_ggnn_cell_fwd saves and gh_ggnn_cell_bwd computes (csrc/cell_ops.hip), written out: the reference of
+# tests/test_gpu_cell_paths.py and tests/test_gpu_cell_bwd_nodx.py, checked on its own against autograd through the oracle's cell
+# and against the reference's golden by tests/test_cell_restatement_cpu.py.
+CELL_W = ("p", "z0", "z1", "r0", "r1", "h0", "h1")
+CELL_B = ("z0", "z1", "r0", "r1", "h0", "h1")
+CELL_SAVED = ("xp", "a", "z", "rr", "rx", "hh")
+CELL_SCRATCH = ("dhp", "dzp", "drp", "dxp", "da")
+
+
+def cell_forward_f64(adj, x, w, b):
+    """adj (N,R,R), x (N,R,din) the masked input rows, w / b: the seven weights and six biases by CELL_W / CELL_B name ->
+    dict of the saved streams xp, a, z, rr, rx, hh and `out` (wrapper.py:188-208), float64."""
+    W = {k: v.double() for k, v in w.items()}
+    B = {k: v.double() for k, v in b.items()}
+    adj, x = adj.double(), x.double()
+    xp = x @ W["p"].t()
+    a = adj @ xp
+    z = torch.sigmoid(a @ W["z0"].t() + B["z0"] + xp @ W["z1"].t() + B["z1"])
+    rr = torch.sigmoid(a @ W["r0"].t() + B["r0"] + xp @ W["r1"].t() + B["r1"])
+    rx = rr * xp
+    hh = torch.tanh(a @ W["h0"].t() + B["h0"] + rx @ W["h1"].t() + B["h1"])
+    return dict(xp=xp, a=a, z=z, rr=rr, rx=rx, hh=hh, out=hh * z + xp * (1 - z))
+
+
+def cell_backward_f64(adj, x, g, w, b, saved=None, scratch=None):
+    """adj (N,R,R), x (N,R,din) the masked input rows, g (N,R,h): every gradient of the cell, by hand, in float64 ->
+    (dw by CELL_W name, db by CELL_B name, dx).  saved: the forward's streams to start from (default: cell_forward_f64 of
+    the same inputs); scratch: a dict that receives the five scratch streams as the written-out chain leaves them (dhp, dzp,
+    drp; dxp after every term including A_hat^T da; da summed over the three gates)."""
+    W = {k: v.double() for k, v in w.items()}
+    adj, x, g = adj.double(), x.double(), g.double()
+    s = cell_forward_f64(adj, x, w, b) if saved is None else {k: saved[k].double() for k in CELL_SAVED}
+    xp, a, z, r, rx, hh = (s[k] for k in CELL_SAVED)
+    dhp = g * z * (1 - hh * hh)
+    dzp = g * (hh - xp) * z * (1 - z)
+    dxp = g * (1 - z)
+    da = dhp @ W["h0"]
+    drx = dhp @ W["h1"]
+    drp = drx * xp * r * (1 - r)
+    dxp = dxp + drx * r
+    da = da + dzp @ W["z0"] + drp @ W["r0"]
+    dxp = dxp + dzp @ W["z1"] + drp @ W["r1"]
+    dxp = dxp + adj.transpose(1, 2) @ da
+    tn = lambda p, q: torch.einsum("nri,nrj->ij", p, q)
+    dw = {"p": tn(dxp, x), "z0": tn(dzp, a), "z1": tn(dzp, xp), "r0": tn(drp, a), "r1": tn(drp, xp), "h0": tn(dhp, a),
+          "h1": tn(dhp, rx)}
+    col = lambda p: p.sum((0, 1))
+    db = {"z0": col(dzp), "z1": col(dzp), "r0": col(drp), "r1": col(drp), "h0": col(dhp), "h1": col(dhp)}
+    if scratch is not None:
+        scratch.update(dhp=dhp, dzp=dzp, drp=drp, dxp=dxp, da=da)
+    return dw, db, dxp @ W["p"]
+
+
 # ----------------------------------------------------------------------------- concat attention restatement (float64, tests only)
 # What gh_concat_att_fwd computes and saves, as plain torch ops; the reference of tests/test_gpu_concat_att_paths.py, checked
 # on its own against the oracle and the reference's goldens by tests/test_concat_restatement_cpu.py.

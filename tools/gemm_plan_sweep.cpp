@@ -1,10 +1,13 @@
 // Walks the GEMM planner (get_amd/csrc/gemm_plan.h: Batch's tile choice, the fast-path rule, the two split-K plans with their
 // workspace layout, the kernel configuration and the grid) over shape classes on the CPU, checks the invariants the kernels rely
-// on, and asserts the plans the project already relies on exactly.  Exits non-zero on any violation.
+// on, and asserts the plans the project already relies on exactly, among them every launch of the GGNN cell entries
+// for the cases of tests/test_gpu_cell_paths.py.  Exits non-zero on any violation.  With an argument it also prints
+// the cell cases' launches.
 // Plain host C++:
 //   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/gemm_plan_sweep.cpp -o gemm_plan_sweep
 #include "../get_amd/csrc/gemm_plan.h"
 #include <stdio.h>
+#include <string>
 #include <vector>
 
 using namespace gh;
@@ -353,10 +356,354 @@ static void named_plans() {
   }
 }
 
-int main() {
+// ---- (c) the launches of the GGNN cell entries (cell_ops.hip cell_fwd_impl / cell_bwd_impl as the public entries call them: one
+// stream, no fused next cell, no second row buffer), for every case of tests/test_gpu_cell_paths.py.  A launch is written as
+//   NT:  <tile> [xK(T)F] fast|generic pN tM      K chunks of T K tiles and nt_finish_kernel's shape F (1 = a workgroup per row)
+//   TN:  TN kK*R ws|atomic cs+|cs-|-- fast|generic pN      K chunks of R rows; partial tiles in the workspace or atomics; column
+//        sums fused into the launch (cs+), wanted but left to launch_colsum3 (cs-), not wanted (--)
+// and a call as its launches in order.  NULL_ / MIS: an aligned address and one a float past a 16-byte boundary.
+static float* const MIS = PTR + 1;
+struct CellCase {
+  int M, seg0, din, h;          // rows of the launches; seg0 > 0: node-compact with padding rows (Problem::seg0_rows)
+  int ids, drop, score, sdrop;  // forward: gathered rows, input dropout, fused scorer projection (and its dropout)
+  int mode;                     // GEMM mode
+  size_t ws;                    // split-K bytes of the workspace (0: none)
+  int mis;                      // forward: 0 none, 1 w_z0, 2 b_r0, 3 xp, 4 out; backward: 1 = x / the table
+  int elt;                      // bf16 storage entries
+};
+static void add_blocks(Built& b, const Problem& p, bool tn, int bm, int bn) {
+  for (int n0 = 0; n0 < p.N; n0 += bn) {      // Batch::add: a block's pointers move by multiples of 4 floats, its alignment stays
+    Problem q = p;
+    q.N = p.N - n0 < bn ? p.N - n0 : bn;
+    if (tn) q.seg[0].vecB = q.elt ? (al16(q.seg[0].B) && q.seg[0].ldb % 8 == 0 && q.N % 8 == 0) : vec_ok(q.seg[0].B, q.seg[0].ldb, q.N);
+    push(b, q, tn, bm);
+  }
+}
+static std::string nt_line(Built& b, const TilePlan& t, bool narrow, int mode, size_t ws) {
+  Launch L = b.L;
+  const NtSplitPlan S = nt_split_plan(L, ws > 0, ws);
+  if (S.ok) { L.ksplit = S.ks; L.kchunk = 16 * S.ct; }
+  const ConfigPlan c = gemm_config(L, false, false, t.big, narrow, t.wide, t.wide256, mode);
+  char buf[128];
+  int n = snprintf(buf, sizeof(buf), "%s", CFG_NAME[c.cfg]);
+  if (S.ok) n += snprintf(buf + n, sizeof(buf) - n, " x%d(%d)%d", S.ks, S.ct, S.finish_split);
+  snprintf(buf + n, sizeof(buf) - n, " %s p%d t%d", fast_ok(b.L, false) ? "fast" : "generic", L.nprob, c.m_tiles);
+  return buf;
+}
+static std::string tn_line(Built& b, const bool* has_cs, int mode, size_t ws) {
+  const TnPlan P = tn_split_plan(b.L, b.tn_pp, b.k_total, has_cs, ws > 0, ws, mode);
+  char buf[128];
+  snprintf(buf, sizeof(buf), "TN%s k%d*%d %s %s %s p%d", b.tn_pp ? " ping-pong" : "", P.ksplit, P.kchunk,
+           (b.tn_pp && !P.use_ws) ? "refused" : P.use_ws ? "ws" : "atomic", P.want_cs ? (P.cs_in_launch ? "cs+" : "cs-") : "--", fast_ok(b.L, true) ? "fast" : "generic", b.L.nprob);
+  return buf;
+}
+static Problem cell_nt(const CellCase& c, int N, int epi, float* C, const float* A, int lda, const float* B, int K, const int32_t* gather = nullptr) {
+  Problem p = make_problem(c.M, N, epi, C, N);
+  p.elt = c.elt;
+  p.seg[0] = make_seg_nt(A, lda, B, K, K, gather, c.elt);
+  return p;
+}
+static std::string cell_fwd_lines(const CellCase& c) {
+  const int h = c.h, din = c.din;
+  float* xp = c.mis == 3 ? MIS : PTR;
+  static const int32_t* const IDS = reinterpret_cast<const int32_t*>(0x20000);
+  const bool wide = c.elt && h % 256 == 0;
+  std::string out;
+  {  // xp = dropout(x) Wp^T
+    const TilePlan t = tile_plan(false, c.M, wide, 7, h, c.mode, NARROW_MASK);
+    Built b; start(b);
+    Problem p = cell_nt(c, h, EPI_STORE, xp, PTR, din, PTR, din, c.ids ? IDS : nullptr);
+    if (c.drop) p.drop_mode = 1;
+    add_blocks(b, p, false, t.bm, t.bn);
+    out += nt_line(b, t, t.narrow, c.mode, c.ws);
+  }
+  {  // z, r
+    const TilePlan t = tile_plan(false, c.M, wide, 1, h, c.mode, NARROW_MASK);
+    Built b; start(b);
+    Problem pz = cell_nt(c, h, EPI_SIGMOID_Z, PTR, PTR, h, c.mis == 1 ? MIS : PTR, h);
+    pz.seg[pz.nseg++] = make_seg_nt(xp, h, PTR, h, h, nullptr, c.elt);
+    pz.bias = PTR; pz.bias2 = PTR;
+    Problem pr = cell_nt(c, h, EPI_SIGMOID_R, PTR, PTR, h, PTR, h);
+    pr.seg[pr.nseg++] = make_seg_nt(xp, h, PTR, h, h, nullptr, c.elt);
+    pr.bias = c.mis == 2 ? MIS : PTR; pr.bias2 = PTR; pr.out1 = PTR; pr.in0 = xp;
+    pz.seg0_rows = pr.seg0_rows = c.seg0;
+    add_blocks(b, pz, false, t.bm, t.bn);
+    add_blocks(b, pr, false, t.bm, t.bn);
+    out += " | " + nt_line(b, t, t.narrow, c.mode, c.ws);
+  }
+  {  // h gate, the convex update and the scorer projection
+    TilePlan t = tile_plan(false, c.M, wide && !c.score, 2, h, c.mode, NARROW_MASK);
+    if (c.score && t.narrow && h > 2 * t.bn) { t.narrow = false; t.bn = 320; }
+    Built b; start(b);
+    Problem ph = cell_nt(c, h, EPI_TANH_H, PTR, PTR, h, PTR, h);
+    ph.seg[ph.nseg++] = make_seg_nt(PTR, h, PTR, h, h, nullptr, c.elt);
+    ph.bias = PTR; ph.bias2 = PTR; ph.out1 = c.mis == 4 ? MIS : PTR; ph.in0 = PTR; ph.in1 = xp;
+    ph.seg0_rows = c.seg0;
+    if (c.score) { ph.w2 = PTR; ph.e = PTR; if (c.sdrop) ph.drop_mode = 2; }
+    if (c.score && h > t.bn && !(t.narrow && h <= 2 * t.bn)) return out + " | refused";      // Batch::add: whole rows only
+    add_blocks(b, ph, false, t.bm, t.bn);
+    out += " | " + nt_line(b, t, t.narrow, c.mode, c.ws);
+  }
+  return out;
+}
+// dx: the caller wants the input gradient; else (with ids) the re-associated path when cell_bwd_impl's conditions hold
+static std::string cell_bwd_lines(const CellCase& c, bool dx) {
+  const int h = c.h, din = c.din, M = c.M;
+  const bool wide = c.elt && h % 256 == 0;
+  static const int32_t* const IDS = reinterpret_cast<const int32_t*>(0x20000);
+  const float* x = c.mis == 1 ? MIS : PTR;
+  const size_t ts_bytes = 20 * (size_t)h * din;
+  // (the workspace as registered: ws is its split-K part, 15/16 of it)
+  const bool nodx = !dx && !c.elt && din <= h && din % 4 == 0 && h % 4 == 0 && c.ws > 0 && c.ws / 2 >= ts_bytes;
+  std::string out;
+  auto tn = [&](int I, int J, const float* B, const int32_t* gatherB) {
+    Problem p = make_problem(I, J, EPI_ATOMIC, PTR, J);
+    p.seg[0] = make_seg_tn(PTR, I, I, B, J, J, M, nullptr, gatherB);
+    p.elt = c.elt;
+    if (c.elt) { p.seg[0].vecA = I % 8 == 0; p.seg[0].vecB = al16(B) && J % 8 == 0; }
+    return p;
+  };
+  if (nodx) {
+    const size_t ws_left = c.ws - ts_bytes;
+    {
+      const TilePlan t = tile_plan(false, M, false, 3, h, c.mode, NARROW_MASK);
+      Built b; start(b);
+      Problem p1 = cell_nt(c, h, EPI_BWD_DRX, PTR, PTR, h, PTR, h);
+      p1.out1 = PTR; p1.in0 = PTR; p1.in1 = PTR;
+      add_blocks(b, p1, false, t.bm, t.bn);
+      out += nt_line(b, t, t.narrow, c.mode, c.ws);
+    }
+    const float* X = (c.ids || c.drop) ? PTR : x;
+    {
+      Built b; start(b);
+      bool has_cs[GH_MAX_PROBLEMS] = {};
+      const Problem ps[4] = {tn(h, din, X, nullptr), tn(h, din, X, nullptr), tn(h, h, PTR, nullptr), tn(h, din, X, nullptr)};
+      for (int i = 0; i < 4; ++i) { add_blocks(b, ps[i], true, 64, 320); if (i < 3) has_cs[b.L.nprob - 1] = true; }
+      out += " | " + tn_line(b, has_cs, c.mode, ws_left);
+    }
+    {
+      Built b; start(b);
+      bool has_cs[GH_MAX_PROBLEMS] = {};
+      for (int i = 0; i < 3; ++i) add_blocks(b, tn(h, din, PTR, nullptr), true, 64, 320);
+      out += " | " + tn_line(b, has_cs, c.mode, ws_left);
+    }
+    return out;
+  }
+  {  // da = dhp Wh0 ; d(r xp) = dhp Wh1
+    const TilePlan t = tile_plan(false, M, wide, 3, h, c.mode, NARROW_MASK);
+    Built b; start(b);
+    Problem p0 = cell_nt(c, h, EPI_STORE, PTR, PTR, h, PTR, h);
+    Problem p1 = cell_nt(c, h, EPI_BWD_DRX, PTR, PTR, h, PTR, h);
+    p1.out1 = PTR; p1.in0 = PTR; p1.in1 = PTR;
+    add_blocks(b, p0, false, t.bm, t.bn);
+    add_blocks(b, p1, false, t.bm, t.bn);
+    out += nt_line(b, t, t.narrow, c.mode, c.ws);
+  }
+  {  // da += dzp Wz0 + drp Wr0 ; dxp += dzp Wz1 + drp Wr1
+    const TilePlan t = tile_plan(false, M, wide, 4, h, c.mode, NARROW_MASK);
+    Built b; start(b);
+    for (int i = 0; i < 2; ++i) {
+      Problem p = cell_nt(c, h, EPI_STORE, PTR, PTR, h, PTR, h);
+      p.seg[p.nseg++] = make_seg_nt(PTR, h, PTR, h, h, nullptr, c.elt);
+      p.accumulate = 1;
+      add_blocks(b, p, false, t.bm, t.bn);
+    }
+    out += " | " + nt_line(b, t, t.narrow, c.mode, c.ws);
+  }
+  if (dx) {
+    const TilePlan t = tile_plan(false, M, wide && din % 256 == 0, 5, din, c.mode, NARROW_MASK);
+    Built b; start(b);
+    Problem p = cell_nt(c, din, EPI_STORE, PTR, PTR, h, PTR, h);
+    p.io = 0;
+    if (c.drop) p.drop_mode = 3;
+    add_blocks(b, p, false, t.bm, t.bn);
+    out += " | " + nt_line(b, t, t.narrow, c.mode, c.ws);
+  }
+  {  // the seven weight gradients in one Batch
+    std::string lines;
+    Built b; start(b);
+    bool has_cs[GH_MAX_PROBLEMS] = {};
+    const bool cs = c.elt ? true : h % 4 == 0;
+    auto flush = [&]() { lines += " | " + tn_line(b, has_cs, c.mode, c.ws); start(b); for (bool& v : has_cs) v = false; };
+    auto add = [&](const Problem& p, bool want) {
+      const bool pp = tn_pp_ok(p, true, c.ws > 0);
+      if (b.L.nprob > 0 && pp != b.tn_pp) flush();      // (a launch is one kernel)
+      for (int n0 = 0; n0 < p.N; n0 += pp ? (1 << 30) : 320) {
+        if (b.L.nprob == GH_MAX_PROBLEMS) flush();
+        Problem q = p;
+        q.N = pp ? p.N : (p.N - n0 < 320 ? p.N - n0 : 320);
+        if (!c.elt) q.seg[0].vecB = vec_ok(q.seg[0].B, q.seg[0].ldb, q.N);
+        b.tn_pp = pp;
+        push(b, q, true, 64);
+      }
+      if (want) has_cs[b.L.nprob - 1] = true;
+    };
+    for (int i = 0; i < 6; ++i) add(tn(h, h, PTR, nullptr), cs && i % 2 == 0);
+    const bool gathered = (c.ids || c.drop || c.elt) && din <= h;      // operand rows materialised by gather_rows into `da`
+    add(tn(h, din, gathered ? PTR : x, (!gathered && c.ids) ? IDS : nullptr), false);
+    flush();
+    out += lines;
+  }
+  return out;
+}
+struct CellWant { const char* name; CellCase c; int bwd; const char* want; };      // bwd: 0 forward, 1 backward with dx, 2 without
+static void named_cell_plans(bool print) {
+  const size_t W = WS_DEFAULT, W1 = WS_BYTES[1];
+  static const CellWant wants[] = {
+    {"fwd (3,20,8,8) x", {60,0,8,8,0,0,0,0,0,W,0,0}, 0,
+     "32x320 fast p1 t2 | 32x320 fast p2 t2 | 32x320 fast p1 t2"},
+    {"fwd (3,20,8,8) ids drop", {60,0,8,8,1,1,0,0,0,W,0,0}, 0,
+     "32x320 fast p1 t2 | 32x320 fast p2 t2 | 32x320 fast p1 t2"},
+    {"fwd (3,20,12,20) x", {60,0,12,20,0,0,0,0,0,W,0,0}, 0,
+     "32x320 fast p1 t2 | 32x320 fast p2 t2 | 32x320 fast p1 t2"},
+    {"fwd (3,20,12,20) ids drop", {60,0,12,20,1,1,0,0,0,W,0,0}, 0,
+     "32x320 fast p1 t2 | 32x320 fast p2 t2 | 32x320 fast p1 t2"},
+    {"fwd (3,20,12,20) x fp32x3p", {60,0,12,20,0,0,0,0,3,W,0,0}, 0,
+     "32x320 fast p1 t2 | 32x320 fast p2 t2 | 32x320 fast p1 t2"},
+    {"fwd (2,100,64,64) split", {200,0,64,64,0,0,0,0,0,W,0,0}, 0,
+     "32x320 fast p1 t7 | 32x320 x2(4)0 fast p2 t7 | 32x320 x2(4)0 fast p1 t7"},
+    {"fwd (2,100,64,64) split fp32x3p", {200,0,64,64,0,0,0,0,3,W,0,0}, 0,
+     "32x320 fast p1 t7 | 32x320 x2(4)0 fast p2 t7 | 32x320 x2(4)0 fast p1 t7"},
+    {"fwd (2,100,300,300) split", {200,0,300,300,0,0,0,0,0,W,0,0}, 0,
+     "32x320 x4(5)0 fast p1 t7 | 32x320 x8(5)0 fast p2 t7 | 32x320 x8(5)0 fast p1 t7"},
+    {"fwd (3,20,64,512) split", {60,0,64,512,0,0,0,0,0,W,0,0}, 0,
+     "32x320 fast p2 t2 | 32x320 x16(4)1 fast p4 t2 | 32x320 x16(4)1 fast p2 t2"},
+    {"fwd (2,100,64,64) compact", {200,133,64,64,0,0,0,0,0,W,0,0}, 0,
+     "32x320 fast p1 t7 | 32x320 fast p2 t7 | 32x320 fast p1 t7"},
+    {"fwd (2,100,64,64) score", {200,0,64,64,0,0,1,1,0,W,0,0}, 0,
+     "32x320 fast p1 t7 | 32x320 x2(4)0 fast p2 t7 | 32x320 fast p1 t7"},
+    {"fwd (2,100,64,64) drop", {200,0,64,64,0,1,0,0,0,W,0,0}, 0,
+     "32x320 fast p1 t7 | 32x320 x2(4)0 fast p2 t7 | 32x320 x2(4)0 fast p1 t7"},
+    {"fwd (2,100,300,300) drop", {200,0,300,300,0,1,0,0,0,W,0,0}, 0,
+     "32x320 fast p1 t7 | 32x320 x8(5)0 fast p2 t7 | 32x320 x8(5)0 fast p1 t7"},
+    {"fwd (3,20,300,1) generic", {60,0,300,1,0,0,0,0,0,W,0,0}, 0,
+     "32x320 generic p1 t2 | 32x320 generic p2 t2 | 32x320 generic p1 t2"},
+    {"fwd (3,20,6,6) generic", {60,0,6,6,0,0,0,0,0,W,0,0}, 0,
+     "32x320 generic p1 t2 | 32x320 generic p2 t2 | 32x320 generic p1 t2"},
+    {"fwd (3,20,12,30) generic", {60,0,12,30,0,0,0,0,0,W,0,0}, 0,
+     "32x320 generic p1 t2 | 32x320 generic p2 t2 | 32x320 generic p1 t2"},
+    {"fwd (3,20,12,30) generic compact", {60,27,12,30,0,0,0,0,0,W,0,0}, 0,
+     "32x320 generic p1 t2 | 32x320 generic p2 t2 | 32x320 generic p1 t2"},
+    {"fwd (3,20,8,8) w misaligned", {60,0,8,8,0,0,0,0,0,W,1,0}, 0,
+     "32x320 fast p1 t2 | 32x320 generic p2 t2 | 32x320 fast p1 t2"},
+    {"fwd (3,20,8,8) bias misaligned", {60,0,8,8,0,0,0,0,0,W,2,0}, 0,
+     "32x320 fast p1 t2 | 32x320 generic p2 t2 | 32x320 fast p1 t2"},
+    {"fwd (3,20,8,8) xp misaligned", {60,0,8,8,0,0,0,0,0,W,3,0}, 0,
+     "32x320 generic p1 t2 | 32x320 generic p2 t2 | 32x320 generic p1 t2"},
+    {"fwd (3,20,8,8) out misaligned", {60,0,8,8,0,0,0,0,0,W,4,0}, 0,
+     "32x320 fast p1 t2 | 32x320 fast p2 t2 | 32x320 generic p1 t2"},
+    {"fwd (3,20,6,6) score", {60,0,6,6,0,0,1,0,0,W,0,0}, 0,
+     "32x320 generic p1 t2 | 32x320 generic p2 t2 | 32x320 generic p1 t2"},
+    {"fwd (3,20,8,480) score", {60,0,8,480,0,0,1,0,0,W,0,0}, 0,
+     "32x320 fast p2 t2 | 32x320 x15(4)0 fast p4 t2 | refused"},
+    {"fwd (82,100,48,160)", {8200,0,48,160,0,0,0,0,0,W,0,0}, 0,
+     "64x160 fast p1 t129 | 64x160 fast p2 t129 | 64x160 fast p1 t129"},
+    {"fwd (82,100,300,300)", {8200,0,300,300,0,0,0,0,0,W,0,0}, 0,
+     "64x160 fast p2 t129 | 64x160 fast p4 t129 | 64x160 fast p2 t129"},
+    {"fwd (82,100,300,300) fp32x3p", {8200,0,300,300,0,0,0,0,3,W,0,0}, 0,
+     "32x320 fast p1 t257 | 32x320 fast p2 t257 | 32x320 fast p1 t257"},
+    {"fwd (120,100,48,160) fp32x3p", {12000,0,48,160,0,0,0,0,3,W,0,0}, 0,
+     "32x320 fast p1 t375 | 64x320 fast p2 t188 | 32x320 fast p1 t375"},
+    {"fwd (82,100,300,300) score", {8200,0,300,300,0,0,1,1,0,W,0,0}, 0,
+     "64x160 fast p2 t129 | 64x160 fast p4 t129 | 64x160 fast p2 t129"},
+    {"fwd (82,100,300,300) score compact 8192", {8192,7868,300,300,0,0,1,1,0,W,0,0}, 0,
+     "64x160 fast p2 t128 | 64x160 fast p4 t128 | 64x160 fast p2 t128"},
+    {"fwd (82,100,300,300) score compact 8198", {8198,7868,300,300,0,0,1,1,0,W,0,0}, 0,
+     "64x160 fast p2 t129 | 64x160 fast p4 t129 | 64x160 fast p2 t129"},
+    {"fwd (82,100,48,160) compact 8192", {8192,7868,48,160,0,0,0,0,0,W,0,0}, 0,
+     "64x160 fast p1 t128 | 64x160 fast p2 t128 | 64x160 fast p1 t128"},
+    {"fwd (250,100,300,300)", {25000,0,300,300,0,0,0,0,0,W,0,0}, 0,
+     "64x320 fast p1 t391 | 64x320 fast p2 t391 | 64x160 fast p2 t391"},
+    {"fwd (251,100,300,300)", {25100,0,300,300,0,0,0,0,0,W,0,0}, 0,
+     "64x320 fast p1 t393 | 32x320 fast p2 t785 | 64x160 fast p2 t393"},
+    {"fwd (82,100,300,300) compact 3718", {3718,0,300,300,0,0,0,0,0,W,0,0}, 0,
+     "32x320 fast p1 t117 | 32x320 fast p2 t117 | 32x320 fast p1 t117"},
+    {"fwd (82,100,300,300) compact 8200 of 3718", {8200,3718,300,300,0,0,0,0,0,W,0,0}, 0,
+     "64x160 fast p2 t129 | 64x160 fast p4 t129 | 64x160 fast p2 t129"},
+    {"fwd (3,20,12,20) compact 27", {27,0,12,20,0,0,0,0,0,W,0,0}, 0,
+     "32x320 fast p1 t1 | 32x320 fast p2 t1 | 32x320 fast p1 t1"},
+    {"fwd (3,20,12,20) compact 60 of 27", {60,27,12,20,0,0,0,0,0,W,0,0}, 0,
+     "32x320 fast p1 t2 | 32x320 fast p2 t2 | 32x320 fast p1 t2"},
+    {"bwd dx (3,20,12,20)", {60,0,12,20,0,0,0,0,0,W,0,0}, 1,
+     "32x320 fast p2 t2 | 32x320 fast p2 t2 | 32x320 fast p1 t2 | TN k1*64 atomic cs- fast p7"},
+    {"bwd dx (3,20,12,20) fp32x3p", {60,0,12,20,0,0,0,0,3,W,0,0}, 1,
+     "32x320 fast p2 t2 | 32x320 fast p2 t2 | 32x320 fast p1 t2 | TN k1*64 atomic cs- fast p7"},
+    {"bwd dx (2,100,64,64)", {200,0,64,64,0,0,0,0,0,W,0,0}, 1,
+     "32x320 fast p2 t7 | 32x320 x2(4)0 fast p2 t7 | 32x320 fast p1 t7 | TN k1*208 atomic cs- fast p7"},
+    {"bwd dx (2,100,64,64) fp32x3p", {200,0,64,64,0,0,0,0,3,W,0,0}, 1,
+     "32x320 fast p2 t7 | 32x320 x2(4)0 fast p2 t7 | 32x320 fast p1 t7 | TN k1*208 atomic cs- fast p7"},
+    {"bwd dx (3,20,16,128)", {60,0,16,128,0,0,0,0,0,W,0,0}, 1,
+     "32x320 x2(4)0 fast p2 t2 | 32x320 x4(4)0 fast p2 t2 | 32x320 x2(4)0 fast p1 t2 | TN k1*64 atomic cs- fast p7"},
+    {"bwd dx (82,100,300,300)", {8200,0,300,300,0,0,0,0,0,W,0,0}, 1,
+     "64x160 fast p4 t129 | 64x160 fast p4 t129 | 64x160 fast p2 t129 | TN k24*352 ws cs+ fast p7"},
+    {"bwd dx (3,20,12,20) drop", {60,0,12,20,0,1,0,0,0,W,0,0}, 1,
+     "32x320 fast p2 t2 | 32x320 fast p2 t2 | 32x320 fast p1 t2 | TN k1*64 atomic cs- fast p7"},
+    {"bwd dx (3,20,12,20) ids", {60,0,12,20,1,0,0,0,0,W,0,0}, 1,
+     "32x320 fast p2 t2 | 32x320 fast p2 t2 | 32x320 fast p1 t2 | TN k1*64 atomic cs- fast p7"},
+    {"bwd dx (3,20,12,20) ids drop table misaligned", {60,0,12,20,1,1,0,0,0,W,1,0}, 1,
+     "32x320 fast p2 t2 | 32x320 fast p2 t2 | 32x320 fast p1 t2 | TN k1*64 atomic cs- fast p7"},
+    {"bwd dx (3,20,6,6)", {60,0,6,6,0,0,0,0,0,W,0,0}, 1,
+     "32x320 generic p2 t2 | 32x320 generic p2 t2 | 32x320 generic p1 t2 | TN k1*64 atomic -- generic p7"},
+    {"bwd dx (3,7,6,6) ids", {21,0,6,6,1,0,0,0,0,W,0,0}, 1,
+     "32x320 generic p2 t1 | 32x320 generic p2 t1 | 32x320 generic p1 t1 | TN k1*32 atomic -- generic p7"},
+    {"bwd dx (3,20,12,30)", {60,0,12,30,0,0,0,0,0,W,0,0}, 1,
+     "32x320 generic p2 t2 | 32x320 generic p2 t2 | 32x320 generic p1 t2 | TN k1*64 atomic -- generic p7"},
+    {"bwd dx (3,20,20,12) x", {60,0,20,12,0,0,0,0,0,W,0,0}, 1,
+     "32x320 fast p2 t2 | 32x320 fast p2 t2 | 32x320 fast p1 t2 | TN k1*64 atomic cs- fast p7"},
+    {"bwd dx (3,20,20,12) ids", {60,0,20,12,1,0,0,0,0,W,0,0}, 1,
+     "32x320 fast p2 t2 | 32x320 fast p2 t2 | 32x320 fast p1 t2 | TN k1*64 atomic cs- generic p7"},
+    {"bwd nodx (3,20,12,20)", {60,0,12,20,1,0,0,0,0,W,0,0}, 2,
+     "32x320 fast p1 t2 | TN k1*64 atomic cs- fast p4 | TN k1*64 atomic -- fast p3"},
+    {"bwd nodx (82,100,300,300)", {8200,0,300,300,1,1,0,0,0,W,0,0}, 2,
+     "64x160 fast p2 t129 | TN k24*352 ws cs+ fast p4 | TN k24*352 ws -- fast p3"},
+    {"bwd nodx (82,100,48,160)", {8200,0,48,160,1,0,0,0,0,W,0,0}, 2,
+     "64x160 fast p1 t129 | TN k24*352 ws cs+ fast p4 | TN k24*352 ws -- fast p3"},
+    {"bwd nodx (3,20,20,12) din > h", {60,0,20,12,1,0,0,0,0,W,0,0}, 2,
+     "32x320 fast p2 t2 | 32x320 fast p2 t2 | TN k1*64 atomic cs- generic p7"},
+    {"bwd nodx (3,20,6,8) din % 4", {60,0,6,8,1,0,0,0,0,W,0,0}, 2,
+     "32x320 fast p2 t2 | 32x320 fast p2 t2 | TN k1*64 atomic cs- generic p7"},
+    {"bwd nodx (3,20,12,30) h % 4", {60,0,12,30,1,0,0,0,0,W,0,0}, 2,
+     "32x320 generic p2 t2 | 32x320 generic p2 t2 | TN k1*64 atomic -- generic p7"},
+    {"bwd nodx (3,20,12,20) no workspace", {60,0,12,20,1,0,0,0,0,0,0,0}, 2,
+     "32x320 fast p2 t2 | 32x320 fast p2 t2 | TN k1*64 atomic cs- fast p7"},
+    {"bwd nodx (3,20,300,300) 1 MiB", {60,0,300,300,1,0,0,0,0,W1,0,0}, 2,
+     "32x320 x4(5)0 fast p2 t2 | 32x320 fast p2 t2 | TN k1*64 atomic cs- fast p7"},
+    {"bf16 fwd (82,100,48,160)", {8200,0,48,160,0,0,0,0,0,W,0,1}, 0,
+     "64x320 fast p1 t129 | 64x320 fast p2 t129 | 64x320 fast p1 t129"},
+    {"bf16 fwd (82,100,256,256)", {8200,0,256,256,0,0,0,0,0,W,0,1}, 0,
+     "128x256 bf16 fast p1 t65 | 128x256 bf16 fast p2 t65 | 128x256 bf16 fast p1 t65"},
+    {"bf16 fwd (328,100,256,256)", {32800,0,256,256,0,0,0,0,0,W,0,1}, 0,
+     "256x256 bf16 fast p1 t129 | 256x256 bf16 fast p2 t129 | 256x256 bf16 fast p1 t129"},
+    {"bf16 fwd (328,100,256,256) drop", {32800,0,256,256,0,1,0,0,0,W,0,1}, 0,
+     "128x256 bf16 fast p1 t257 | 256x256 bf16 fast p2 t129 | 256x256 bf16 fast p1 t129"},
+    {"bf16 fwd (82,100,64,192)", {8200,0,64,192,0,0,0,0,0,W,0,1}, 0,
+     "64x320 fast p2 t129 | 64x320 fast p4 t129 | 64x320 fast p2 t129"},
+    {"bf16 fwd (90,100,48,160) compact 9000", {9000,8668,48,160,1,0,0,0,0,W,0,1}, 0,
+     "64x320 fast p1 t141 | 64x320 fast p2 t141 | 64x320 fast p1 t141"},
+    {"bf16 bwd (82,100,48,160)", {8200,0,48,160,0,0,0,0,0,W,0,1}, 1,
+     "64x320 fast p2 t129 | 64x320 fast p2 t129 | 64x320 fast p1 t129 | TN k2*4128 ws cs+ fast p7"},
+    {"bf16 bwd (82,100,256,256)", {8200,0,256,256,0,0,0,0,0,W,0,1}, 1,
+     "128x256 bf16 fast p2 t65 | 128x256 bf16 fast p2 t65 | 128x256 bf16 fast p1 t65 | TN k2*4128 ws cs+ fast p7"},
+    {"bf16 bwd (328,100,256,256)", {32800,0,256,256,0,0,0,0,0,W,0,1}, 1,
+     "256x256 bf16 fast p2 t129 | 256x256 bf16 fast p2 t129 | 256x256 bf16 fast p1 t129 | TN ping-pong k31*1088 ws cs+ fast p7"},
+    {"bf16 bwd (82,100,64,192) ids drop", {8200,0,64,192,1,1,0,0,0,W,0,1}, 1,
+     "64x320 fast p4 t129 | 64x320 fast p4 t129 | 64x320 fast p1 t129 | TN k2*4128 ws cs+ fast p7"},
+    {"bf16 bwd (90,100,48,160) compact", {8668,0,48,160,1,0,0,0,0,W,0,1}, 1,
+     "64x320 fast p2 t136 | 64x320 fast p2 t136 | 64x320 fast p1 t136 | TN k2*4352 ws cs+ fast p7"},
+  };
+  for (const CellWant& w : wants) {
+    const std::string got = w.bwd ? cell_bwd_lines(w.c, w.bwd == 1) : cell_fwd_lines(w.c);
+    if (print) printf("CELL %-44s %s\n", w.name, got.c_str());
+    ++g_named;
+    if (got != w.want) { ++g_bad; printf("NAMED CELL PLAN %s:\n   got      %s\n   expected %s\n", w.name, got.c_str(), w.want); }
+  }
+}
+
+int main(int argc, char** argv) {
   sweep_tn();
   sweep_nt();
   named_plans();
+  named_cell_plans(argc > 1);
   for (int c = 0; c < CFG_NCONFIGS; ++c) {
     const Stat& s = g_stat[c];
     if (s.plans) printf("%-14s %9lld plans  ksplit %d .. %d  grid %lld .. %lld\n", CFG_NAME[c], s.plans, s.ks_min, s.ks_max, s.grid_min, s.grid_max);
