@@ -48,11 +48,14 @@ constexpr int RNN_DG_PITCH = 4 * RNN_CHUNK + 4;              // [16][4][256] + 4
 
 __host__ __device__ inline int rnn_pitch(int h) { return pitch_kc(up16(h)); }      // LDS row pitch of the h_{t-1} / w_hh tiles
 
-// never overflows: exp of a non-positive argument only
+// never overflows: exp of a non-positive argument only.  Saturates to EXACT 0 / 1 (include/get_hip.h): towards -inf the value
+// e s is e itself once s == 1, and fp32 denormals are kept on gfx950, so below ln(2^-126) = -87.34 it would be a denormal
+// (3.8e-44 at -100); such a result is sent to 0.  Every normal result is the one the plain expression gives, bit for bit.
+// The compare and select cost the forward 0.5 - 1.4 %; testing x instead of e measured the same.
 __device__ __forceinline__ float rnn_sigmoid(float x) {
   const float e = expf(-fabsf(x));
   const float s = 1.f / (1.f + e);
-  return x >= 0.f ? s : e * s;
+  return x >= 0.f ? s : (e < 1.17549435e-38f ? 0.f : e * s);
 }
 
 // s_len[i] = clamped length, s_row[i] = tensor row of sequence slot i of this tile (-1: no such sequence)

@@ -433,7 +433,8 @@ int gh_add_layernorm_bwd(const float* x, const float* res /*NULL ok*/, const flo
  * last step of the direction; zeros for an empty sequence -- where pack_padded_sequence raises).  gates [dirs][n][t_in][4h]
  * (post-activation), c [dirs][n][t_in][h] and h_prev [dirs][n][t_in][h] (the hidden state that ENTERED step t, zeros at t >= len)
  * are saved for the backward when all three are given (all NULL: inference).  Rows t >= len of gates and c are not written.
- * The sigmoid takes exp of non-positive arguments only: saturated pre-activations give exact 0 / 1, never NaN.
+ * The sigmoid takes exp of non-positive arguments only: saturated pre-activations give exact 0 / 1, never NaN -- exactly 1 from
+ * about +17 on, exactly 0 below ln(2^-126) = -87.34, where the value would be an fp32 denormal (every normal value is kept).
  * Limits: h <= 1024, t_in <= 4096, t_out <= 4096, dirs 1 or 2, any n; anything beyond is rejected and nothing is written. */
 int gh_lstm_seq_fwd(const float* gx0, const float* gx1 /*NULL ok*/, int ldgx, const float* w_hh0, const float* w_hh1 /*NULL ok*/,
                     const int32_t* lens, const int32_t* order /*NULL ok*/, int n, int t_in, int t_out, int h, int dirs,
@@ -443,8 +444,10 @@ int gh_lstm_seq_fwd(const float* gx0, const float* gx1 /*NULL ok*/, int ldgx, co
  * and g_hn [dirs][n][h] (NULL ok), walking time the other way:
  *   dh = g_y[t] + dh_rec (+ g_hn at the direction's last step);  dc += dh o (1 - tanh(c_t)^2);  di = dc g i (1 - i);
  *   df = dc c_{t-1} f (1 - f);  dg = dc i (1 - g^2);  do = dh tanh(c_t) o (1 - o);  dh_rec = dgates_t W_hh;  dc <- dc f
- * dgates [dirs][n][t_in][4h] is the gradient of gx: every element is written, exact zeros at t >= len.  The caller forms
- * dW_hh = dgates^T h_prev per direction with gh_linear_bwd (dx = NULL, x = h_prev, g = dgates).  Same limits as the forward. */
+ * dgates [dirs][n][t_in][4h] is the gradient of gx: every element of every processed sequence is written, exact zeros at
+ * t >= len (also in rows [t_out, t_in) when t_out < t_in).  The rows of a sequence that `order` skips (an entry outside [0, n)
+ * where its row would have stood) are NOT written, as in the forward.  The caller forms dW_hh = dgates^T h_prev per direction
+ * with gh_linear_bwd (dx = NULL, x = h_prev, g = dgates).  Same limits as the forward. */
 int gh_lstm_seq_bwd(const float* w_hh0, const float* w_hh1 /*NULL ok*/, const int32_t* lens, const int32_t* order /*NULL ok*/,
                     int n, int t_in, int t_out, int h, int dirs, const float* g_y /*NULL ok*/, int ldgy,
                     const float* g_hn /*NULL ok*/, const float* gates, const float* c, float* dgates, gh_stream_t stream);
@@ -462,7 +465,7 @@ int gh_lstm_seq_bwd(const float* w_hh0, const float* w_hh1 /*NULL ok*/, const in
  * (the state after the last step of the direction; zeros for an empty sequence).  Saved for the backward when all three are
  * given (all NULL: inference): gates [dirs][n][t_in][3h] (post-activation r, z, n), an [dirs][n][t_in][h] (a_n, b_hn included)
  * and h_prev [dirs][n][t_in][h] (the hidden state that ENTERED step t, zeros at t >= len).  Rows t >= len of gates and an are
- * not written.  The sigmoid takes exp of non-positive arguments only: saturated pre-activations give exact 0 / 1, never NaN.
+ * not written.  The sigmoid is the LSTM's: saturated pre-activations give exact 0 / 1 (1 from about +17 on, 0 below -87.34), never NaN.
  * Limits: h <= 1024, t_in <= 4096, t_out <= 4096, dirs 1 or 2, any n; anything beyond is rejected and nothing is written. */
 int gh_gru_seq_fwd(const float* gx0, const float* gx1 /*NULL ok*/, int ldgx, const float* w_hh0, const float* w_hh1 /*NULL ok*/,
                    const float* b_hh0, const float* b_hh1 /*NULL ok*/, const int32_t* lens, const int32_t* order /*NULL ok*/,
@@ -472,7 +475,8 @@ int gh_gru_seq_fwd(const float* gx0, const float* gx1 /*NULL ok*/, int ldgx, con
  * (NULL ok), walking time the other way.  With dh = g_y[t] + dh_carry (+ g_hn at the direction's last step):
  *   dn_pre = dh (1 - z) (1 - n^2);  dz_pre = dh (h_prev - n) z (1 - z);  dr_pre = dn_pre a_n r (1 - r);  da_n = dn_pre r;
  *   dh_carry = dh z + [dr_pre, dz_pre, da_n] W_hh
- * Two outputs, each [dirs][n][t_in][3h], every element written, exact zeros at t >= len:
+ * Two outputs, each [dirs][n][t_in][3h], every element of every processed sequence written, exact zeros at t >= len (the rows
+ * of a sequence that `order` skips are NOT written, as in the forward):
  *   dgx = [dr_pre, dz_pre, dn_pre]   the gradient of gx (db_ih, dW_ih and dx follow from the input projection's backward)
  *   da  = [dr_pre, dz_pre, da_n]     the gradient of the recurrent pre-activations a
  * The caller forms dW_hh = da^T h_prev AND db_hh = colsum(da) per direction with ONE gh_linear_bwd (dx = NULL, x = h_prev,

@@ -3,7 +3,9 @@ float64 restatement the GPU tests compare the kernels with (tests/rnn_ref.py) re
 the drop-in's constructor builds the reference's state_dict for every configuration in tests/golden/lstm_contract.json /
 gru_contract.json and initialises a stand-alone module as the reference does (the GRU: as the reference's constructor does
 once its one raising line runs), the C-ABI declares and binds the two recurrence entries, the shim exports the classes, and
-the modules refuse CPU tensors."""
+the modules refuse CPU tensors.  The per-step restatement at the kernels' interface (lstm_steps64 / gru_steps64, what
+tests/test_gpu_rnn_paths.py compares the four recurrence entries with) agrees with lstm64 / gru64 and their autograd, and its
+own fp32 evaluation stays within half of that file's elementwise bound at every one of its cases."""
 import os
 import re
 
@@ -11,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.rnn_ref import CELLS
+from tests.rnn_ref import ARG_CASES, BWD_STREAMS, CELLS, CHAIN_CASES, FWD_STREAMS, STEPS, WIDTH_CASES, case_name, case_reference
 from tests.util import golden_ratio, load_golden, run_in_fresh_interpreter
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -177,3 +179,73 @@ def test_refuses_cpu_tensors_and_bad_lengths(cell):
         m((x, torch.tensor([5, 0]), idx, idx), max_len=5)
     with pytest.raises(ValueError):
         m((x, torch.tensor([5, 3]), idx, idx), max_len=4)
+
+
+# ----------------------------------------------------------------------------- the per-step restatement (tests/rnn_ref.py)
+@pytest.fixture(params=list(CELLS))
+def kind(request):
+    return request.param
+
+
+def _names(kind, bidirectional):
+    return [f"{k}_l0{sfx}" for sfx in (("", "_reverse") if bidirectional else ("",)) for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+
+
+@pytest.mark.parametrize("shape", [(5, 7, 6, 4, 7), (19, 6, 3, 9, 8)], ids=["b5-l7-h4", "b19-l6-h9-t8"])
+@pytest.mark.parametrize("bidirectional", [False, True], ids=["uni", "bi"])
+def test_steps_agree_with_the_encoder_restatement(kind, shape, bidirectional):
+    """Fed with gx = x W_ih^T + b, the per-step function gives lstm64's / gru64's y and h; with W_ih a selection of x's columns
+    (x = [gx0 | gx1], so that the gradient of x IS the gradient of gx) autograd through lstm64 / gru64 gives its dgates / dgx.
+    All to 1e-12 in float64."""
+    B, L, D, H, T = shape
+    G, dirs = CELLS[kind].gates, 2 if bidirectional else 1
+    gen = torch.Generator().manual_seed(B + H)
+    rn = lambda *s: torch.randn(*s, generator=gen, dtype=torch.float64)
+    lens = torch.randint(1, L + 1, (B,), generator=gen)
+    lens[0], lens[1] = L, 1
+    g_y, g_hn = rn(B, T, dirs * H), rn(dirs, B, H)
+
+    def both(params, x, gx):
+        w_hh = [params[f"weight_hh_l0{s}"] for s in ("", "_reverse")[:dirs]]
+        extra = [[params[f"bias_hh_l0{s}"] for s in ("", "_reverse")[:dirs]]] if kind == "gru" else []
+        st = STEPS[kind](gx, w_hh, *extra, lens, L, T, g_y, g_hn, backward=True)
+        x = x.clone().requires_grad_(True)
+        y, hcat = CELLS[kind].ref64(params, x, lens, T, 1, bidirectional)
+        ((y * g_y).sum() + (hcat.view(B, dirs, H).permute(1, 0, 2) * g_hn).sum()).backward()
+        assert float((st["y"] - y.detach()).abs().max()) <= 1e-12
+        assert float((st["h_n"] - hcat.detach().view(B, dirs, H).permute(1, 0, 2)).abs().max()) <= 1e-12
+        return st, x.grad
+
+    # a general input projection: y and h
+    params = {}
+    for k in _names(kind, bidirectional):
+        params[k] = rn(G * H, D) / D ** 0.5 if "weight_ih" in k else rn(G * H, H) / H ** 0.5 if "weight_hh" in k else 0.3 * rn(G * H)
+    x = rn(B, L, D)
+    fold = lambda s: params["bias_ih_l0" + s] + (params["bias_hh_l0" + s] if kind == "lstm" else 0.0)
+    both(params, x, [x @ params["weight_ih_l0" + s].t() + fold(s) for s in ("", "_reverse")[:dirs]])
+    # W_ih selects direction d's columns of x = [gx0 | gx1]: the gradient of x is the gradient of gx
+    gx = [rn(B, L, G * H) for _ in range(dirs)]
+    eye = torch.eye(dirs * G * H, dtype=torch.float64)
+    for d, s in enumerate(("", "_reverse")[:dirs]):
+        params["weight_ih_l0" + s] = eye[d * G * H:(d + 1) * G * H]
+        params["bias_ih_l0" + s] = torch.zeros(G * H, dtype=torch.float64)
+    bias = lambda s: params["bias_hh_l0" + s] if kind == "lstm" else 0.0
+    st, gxgrad = both(params, torch.cat(gx, dim=2), [g + bias(s) for g, s in zip(gx, ("", "_reverse"))])
+    got = st["dgates" if kind == "lstm" else "dgx"]
+    assert float((torch.cat(list(got), dim=2) - gxgrad).abs().max()) <= 1e-12
+    dead = torch.arange(L)[None, :] >= lens.clamp(max=min(L, T))[:, None]
+    assert bool((got[:, dead] == 0).all()) and bool((st["h_prev"][:, dead] == 0).all()) and bool(torch.isnan(st["gates"][:, dead]).all())
+
+
+@pytest.mark.parametrize("c", WIDTH_CASES + ARG_CASES + CHAIN_CASES, ids=case_name)
+def test_fp32_evaluation_stays_within_half_the_elementwise_bound(kind, c):
+    """What makes 1e-5 + 1e-4 |want| a bound on the KERNELS in tests/test_gpu_rnn_paths.py: at every case of that file the
+    restatement evaluated in fp32 on the CPU -- the same operations in another order -- is within half of it, on every forward
+    and backward stream."""
+    want, got = case_reference(kind, c), case_reference(kind, c, torch.float32)
+    worst = 0.0
+    for k in FWD_STREAMS[kind] + BWD_STREAMS[kind]:
+        live = ~torch.isnan(want[k])
+        assert torch.equal(live, ~torch.isnan(got[k])), k
+        worst = max(worst, golden_ratio(got[k][live], want[k][live], 0.5e-5, 0.5e-4, f"{kind} {case_name(c)} {k} fp32 vs float64"))
+    print(f"{kind} {case_name(c)}: fp32 restatement at {worst:.3f} of half the bound")
