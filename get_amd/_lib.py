@@ -121,6 +121,12 @@ SIGNATURES = {
     "gh_match_hist": [_P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
     "gh_embed_fwd": [_P, _P, _P, _I, _I, _I, _P],
     "gh_embed_bwd": [_P, _L, _P, _P, _I, _I, _I, _I, _P, _P, _L, _P],
+    "gh_bert_attention_fwd": [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F, _F, _U, _P, _I, _P, _P],
+    "gh_bert_attention_bwd": [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _U, _P, _P, _I, _P, _I, _P, _I,
+                              _P],
+    "gh_act_fwd": [_P, _P, _I, _I, _I, _P],
+    "gh_act_bwd": [_P, _P, _P, _I, _I, _I, _P],
+    "gh_bert_embed_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     # library-owned RCCL communicator (csrc/comm_ops.hip; librccl is dlopen'ed on first use)
     "gh_comm_unique_id": [_P],
     "gh_comm_init": [_P, _I, _I, _P],

@@ -2,9 +2,9 @@
 // pipeline, the stateless dropout hash, the fast sigmoid / tanh, round-up and LDS-pitch arithmetic and the alignment test of the
 // float4 paths.  Included by the GEMM kernels (gemm.hip.h, and through it gemm_ops.hip,
 // cell_ops.hip, dense_ops.hip), the core streaming files (spmm_ops.hip, gsl_ops.hip, stream_ops.hip, concat_att_ops.hip, eval_ops.hip) and
-// the drop-in kernel files (attention_ops.hip, encoder_ops.hip, mha_ops.hip, rnn_ops.hip, bidaf_ops.hip, match_ops.hip, pair_ops.hip, embed_ops.hip).
-// score_tile.hip.h builds on it: the LDS staging and MFMA helpers of the four files that keep a 16-row score tile in LDS
-// (mha_ops.hip, bidaf_ops.hip, match_ops.hip, pair_ops.hip).
+// the drop-in kernel files (attention_ops.hip, encoder_ops.hip, mha_ops.hip, rnn_ops.hip, bidaf_ops.hip, match_ops.hip, pair_ops.hip, embed_ops.hip, bert_ops.hip).
+// score_tile.hip.h builds on it: the LDS staging and MFMA helpers of the five files that keep a 16-row score tile in LDS
+// (mha_ops.hip, bidaf_ops.hip, match_ops.hip, pair_ops.hip, bert_ops.hip).
 #pragma once
 #include "common.h"
 

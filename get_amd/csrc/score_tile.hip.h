@@ -1,4 +1,4 @@
-// The LDS "score tile" toolkit of the attention files (mha_ops.hip, bidaf_ops.hip, match_ops.hip, pair_ops.hip): one workgroup of
+// The LDS "score tile" toolkit of the attention files (mha_ops.hip, bidaf_ops.hip, match_ops.hip, pair_ops.hip, bert_ops.hip): one workgroup of
 // TILE_THREADS holds a 16-row score tile S [16][n] in LDS, fills it with X Y^T over staged operand chunks and multiplies it
 // into a second operand with the accumulators in registers.  Include after device_utils.h.
 //

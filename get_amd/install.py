@@ -11,7 +11,10 @@ def _module(name, **attrs):
     return m
 
 
-def install():
+def install(bert: bool = False):
+    """bert: also serve ``matchzoo.modules.BertModule`` (get_amd/bert.py).  Off by default: a plain install() keeps serving
+    exactly what it served before, where ``from matchzoo.modules import BertModule`` raises ImportError and callers that probe
+    for it fall back; the vendored pytorch_transformers is never shimmed."""
     import numpy as np
     import torch
     import torch.nn as nn
@@ -40,10 +43,10 @@ def install():
     _module("Models.BiDAF.bidaf_model", BiDAF=M.BiDAF, LSTM=M.LSTM, Linear=M.Linear, KeyWordSettings=KeyWordSettings,
             torch=torch, nn=nn, np=np)
     # the parts sequence-matching baselines are assembled from (basic_fc_model.py:6 imports GaussianKernel from here).
-    # BertModule is not served: it needs the vendored pytorch_transformers, and importing it raises ImportError
+    # BertModule (a local directory or a BertConfig, get_amd/bert.py) only on request: install(bert=True)
     _module("matchzoo.modules", Attention=M.Attention, BidirectionalAttention=M.BidirectionalAttention,
             MatchModule=M.MatchModule, RNNDropout=M.RNNDropout, StackedBRNN=M.StackedBRNN, GaussianKernel=M.GaussianKernel,
-            Matching=M.Matching, torch=torch, nn=nn)
+            Matching=M.Matching, torch=torch, nn=nn, **({"BertModule": M.BertModule} if bert else {}))
     # what those baselines train against and are scored with.  The base fitter imports the metric SUBMODULES
     # (Fitting/densebaseline_fit.py:19-20), so every file of matchzoo/metrics and matchzoo/losses is served under its own name
     from . import ranking as R

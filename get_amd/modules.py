@@ -14,7 +14,7 @@ load unchanged:
   Models/FCWithEvidences/graph_based_semantic_structure.py   Graph_basedSemantiStructure
   Models/BiDAF/bidaf_model.py                  BiDAF
   matchzoo/modules                             Attention, BidirectionalAttention, MatchModule, Matching, GaussianKernel,
-                                               RNNDropout, StackedBRNN
+                                               RNNDropout, StackedBRNN, BertModule (get_amd/bert.py, re-exported here)
   matchzoo/losses                              RankHingeLoss, RankCrossEntropyLoss
 
 (The tensor math outside the reference's modules -- the interaction helpers of torch_utils.py, layers.MovingAverage and the
@@ -1323,3 +1323,7 @@ class RankCrossEntropyLoss(nn.Module):
     @num_neg.setter
     def num_neg(self, value):
         self._num_neg = value
+
+
+# ------------------------------------------------------------------ matchzoo/modules/bert_module.py:9-30 (get_amd/bert.py)
+from .bert import BertConfig, BertModel, BertModule  # noqa: E402,F401

@@ -6,8 +6,9 @@ step runs in libget_hip.so.  All tensors are fp32/contiguous on a ROCm device.
 This file only re-exports the public names: callers look an op up on the package at call time (`ops.att_flow(...)`),
 so a tool may swap one by assignment.  Private helpers and the three mutable flags of `streams` stay in their modules.
 """
-from . import _util, attention, bidaf, dense, embed, graph, match, pair, rank, rnn, streams, weights  # noqa: F401
+from . import _util, attention, bert, bidaf, dense, embed, graph, match, pair, rank, rnn, streams, weights  # noqa: F401
 from .attention import add_layernorm, concat_att, mha_sdpa, query_att, tanh_att  # noqa: F401
+from .bert import bert_attention, bert_embed, gelu, tanh_act  # noqa: F401
 from .bidaf import att_flow, highway  # noqa: F401
 from .dense import (CLS_EXTRA, Segments, adam_step_flat, backward, cls_metrics, cross_entropy, evd_assemble, linear,  # noqa: F401
                     linear_wgrad_bf16, masked_mean, seg_broadcast, seg_pad)

@@ -623,7 +623,8 @@ int gh_evd_assemble_bwd(const float* g, const int32_t* offsets, const void* sour
 /* Out-of-range inputs the kernels clamped for memory safety where the reference would have RAISED (nn.Embedding /
  * nn.CrossEntropyLoss index errors): out_host[0] = labels outside [0, c) seen by gh_cross_entropy, [1] = claim-source ids,
  * [2] = article-source ids outside their table (other than the -1 padding id), [3] = ids outside [0, vocab) among the rows handed
- * to gh_embed_bwd (they contribute nothing there; the padding id is not counted); counted on the CURRENT device since
+ * to gh_embed_bwd (they contribute nothing there; the padding id is not counted) and among the word, position and token-type
+ * ids of gh_bert_embed_fwd; counted on the CURRENT device since
  * the last reset.  Synchronises the device.  A training loop checks it once per epoch (or per step in debug runs): a non-zero
  * count means corrupt input data was trained on as if it were class / row 0 or the last one. */
 int gh_clamp_events(int64_t* out4_host, int reset);
@@ -927,6 +928,56 @@ int gh_embed_fwd(const float* table, const int32_t* ids, float* out, int m, int 
 #define GH_EMBED_CHUNK 128
 int gh_embed_bwd(const float* dx, long long ldx, const int32_t* sorted_ids, const int32_t* perm, int m, int d, int vocab,
                  int padding_idx, float* dtable, float* workspace, long long workspace_floats, gh_stream_t stream);
+
+/* ---- BERT encoder (csrc/bert_ops.hip): pytorch_transformers/modeling_bert.py, which matchzoo/modules/bert_module.py:22-30 wraps ----
+ * Multi-head self-attention with an additive per-key bias, a temperature and dropout on the probabilities, replacing
+ * BertSelfAttention.forward :203-228 (the three transpose_for_scores permutes, both matmul, the division by
+ * sqrt(attention_head_size), the mask addition, the softmax, the dropout and the permute copy of the context):
+ *   q [b][lq][heads * dh], k, v [b][lk][heads * dh], row r of batch i at (i * l + r) * ld, each with its own leading dimension
+ *   (ld >= heads * dh): head h is the column slice [h * dh, (h + 1) * dh), read in place, so the three may be the column
+ *   blocks of one [rows][3 * heads * dh] buffer.  bias [b][lk] fp32 or NULL (= zeros): the host forms (1 - mask) * -10000
+ *   as :603 does.  P = softmax(scale q_h k_h^T + bias) over ALL lk keys, with the reference's roundings (the scaled score is
+ *   rounded, then the bias is added) and the running maximum subtracted: a row whose keys all carry the bias -10000 is the
+ *   softmax of its raw scores (on the 2^-10 grid fp32 has next to 10000), never zeros.
+ *   out [b][lq][heads * dh] (ldo) = (P . keep / (1 - drop_p)) v_h; element (i, h, r, j) of P is kept iff
+ *   drop_hash(seed, ((i * heads + h) * lq + r) * lk + j) >= drop_p * 2^32, the stateless rule of gh_feat_dropout over the
+ *   element index of a [b * heads * lq][lk] tensor (drop_p > 0 needs b * heads * lq * lk < 2^32).  drop_p == 0 runs kernels
+ *   that hold no hash at all.  lse [b][heads][lq] = max + log(sum exp(. - max)) of every row is the only state the backward
+ *   needs besides q, k, v, bias and out: no [lq][lk] tensor is read or written in HBM in either direction.
+ * Limits: 1 <= heads <= 16, lq <= 1024, lk <= 1024, dh <= 512, b * ceil(max(lq, lk) / 16) < 2^31; anything beyond them, a
+ * NULL tensor or a leading dimension below heads * dh is rejected with an error and nothing is written. */
+int gh_bert_attention_fwd(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const float* bias,
+                          int b, int heads, int lq, int lk, int dh, float scale, float drop_p, uint32_t seed,
+                          float* out, int ldo, float* lse, gh_stream_t stream);
+/* Backward of the above (autograd of :203-228) from g_out [b][lq][heads * dh] (ldgo), with P recomputed from q, k, bias and
+ * lse as exp(scale q_h k_h^T + bias - lse) and keep regenerated from (drop_p, seed), per head:
+ *   delta = rowsum(g_out . out) ( = rowsum(P . keep / (1 - p) . dP), so it holds under dropout), dP = g_out v^T,
+ *   dS = P . (keep / (1 - p) . dP - delta), dq = scale dS k, dk = scale dS^T q, dv = (P . keep / (1 - p))^T g_out.
+ * delta [b][heads][lq] is caller-provided scratch of lse's size, written by the first launch and read by the second.  Every
+ * element of dq [b][lq][heads * dh] (lddq), dk, dv [b][lk][heads * dh] (lddk, lddv) is written by one owner: two calls give
+ * the same bits.  Limits and refusals as the forward. */
+int gh_bert_attention_bwd(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const float* bias,
+                          const float* out, int ldo, const float* lse, const float* g_out, int ldgo,
+                          int b, int heads, int lq, int lk, int dh, float scale, float drop_p, uint32_t seed,
+                          float* delta, float* dq, int lddq, float* dk, int lddk, float* dv, int lddv, gh_stream_t stream);
+/* Elementwise activations over a contiguous [rows][n] tensor, 16 bytes per lane where the pointers are 16-byte aligned and
+ * single floats for the last rows * n % 4 elements or an unaligned pointer (in place ok).  GH_ACT_GELU: x * 0.5 * (1 +
+ * erf(x / sqrt(2))), the erf form of :120-126 that BertIntermediate :296 applies; GH_ACT_TANH: BertPooler's nn.Tanh :373.
+ * The backward takes the saved pre-activation: dx = g * act'(x).  The linear layers' bias stays with gh_linear_*. */
+#define GH_ACT_GELU 0
+#define GH_ACT_TANH 1
+int gh_act_fwd(const float* x, float* y, int rows, int n, int mode, gh_stream_t stream);
+int gh_act_bwd(const float* x, const float* g, float* dx, int rows, int n, int mode, gh_stream_t stream);
+/* BertEmbeddings.forward :156-169 without its dropout, in one pass over rows = batch * l tokens: sum[r] = word[ids[r]] +
+ * pos[pos_ids[r]] + type[type_ids[r]] (added in that order) and y[r] = LayerNorm(sum[r]) * gamma + beta (biased variance,
+ * eps inside the root), replacing three lookups, two additions and the LayerNorm.  pos_ids NULL: the column index r % l
+ * (:159-160); type_ids NULL: row 0 of the type table (:161-162).  word [vocab][d], pos [npos][d], type [ntype][d], d <= 2048
+ * (what gh_add_layernorm_bwd, which starts the backward on the saved `sum`, takes).  An id outside its table is clamped into
+ * it for memory safety (nn.Embedding raises) and counted in slot [3] of gh_clamp_events.  Writes sum and y [rows][d], mean
+ * and rstd [rows].  The table gradients are three gh_embed_bwd calls on the gradient gh_add_layernorm_bwd returns. */
+int gh_bert_embed_fwd(const float* word, const float* pos, const float* type, const int32_t* ids, const int32_t* pos_ids,
+                      const int32_t* type_ids, const float* gamma, const float* beta, float eps, int rows, int l, int d,
+                      int vocab, int npos, int ntype, float* sum, float* y, float* mean, float* rstd, gh_stream_t stream);
 
 /* Everything the forward / backward need that is DERIVED from weight matrices, for n matrices in one launch (after the
  * optimiser step): dst_t[i] = src[i]^T as fp32 [cols][rows] (the backward's dX operands), and -- bf16 storage mode, any of the
