@@ -89,6 +89,9 @@ SIGNATURES = {
     "gh_masked_mean_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
     "gh_masked_mean_bwd": [_P, _P, _P, _P, _I, _I, _I, _P],
     "gh_adam_step": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P],
+    "gh_flat_grad_norm_partials": [_L, _P],
+    "gh_flat_grad_norm": [_P, _L, _F, _P, _L, _P, _P],
+    "gh_adamw_step": [_P, _P, _P, _P, _L, _P, _P, _I, _F, _P, _F, _P],
     "gh_set_workspace": [_P, _L],
     "gh_set_stream_workspace": [_P, _P, _L],
     "gh_profile_enable": [_I],

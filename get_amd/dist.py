@@ -67,6 +67,47 @@ def shard_claims(n_claims: int, rank: int, world: int, evd_counts=None):
     return [int(i) for i in np.sort(mine)]          # ascending: keeps the claim-major order of the batch tensors
 
 
+BUCKET_ALIGN = 64      # elements: every slot of a flat bucket starts on a 256-byte boundary, and on a block of gh_adamw_step
+
+
+def slot_offsets(sizes: Sequence[int], align: int = BUCKET_ALIGN):
+    """(offset of every slot, total) of a flat bucket that holds tensors of `sizes` elements in that order, each slot rounded
+    up to `align` elements."""
+    offsets, off = [], 0
+    for n in sizes:
+        offsets.append(off)
+        off += (int(n) + align - 1) // align * align
+    return offsets, off
+
+
+def build_flat_bucket(params: Sequence[torch.Tensor]):
+    """The flat fp32 buffers (p, g, m, v) of `params` in that order, and what FlatTrainer and optim.AdamW do with them: the
+    parameters' values are copied in, ``param.data`` and ``param.grad`` become views into p and g, and the kernels may
+    accumulate straight into the gradient view.  Returns (flat_p, flat_g, flat_m, flat_v, gradient views, offsets).
+    Every parameter starts on a 256-byte boundary of the flat buffers: the kernels take weights and gradients straight from
+    these views and need 16-byte aligned rows (a 2-element bias would otherwise shift everything behind it onto the slow,
+    scalar-load GEMM path); the padding elements stay zero under Adam."""
+    offsets, total = slot_offsets([p.numel() for p in params])
+    dev = params[0].device
+    flat_p, flat_g, flat_m, flat_v = (torch.zeros(total, device=dev, dtype=torch.float32) for _ in range(4))
+    views = []
+    for p, off in zip(params, offsets):
+        n = p.numel()
+        flat_p[off:off + n].copy_(p.data.reshape(-1))
+        p.data = flat_p[off:off + n].view_as(p)
+        gv = flat_g[off:off + n].view_as(p)
+        p.grad = gv
+        p._gh_direct_grad = True          # kernels may accumulate straight into this view (ops.weights._direct)
+        views.append(gv)
+    return flat_p, flat_g, flat_m, flat_v, views, offsets
+
+
+def forward_matrices(model: torch.nn.Module, params: Sequence[torch.Tensor]):
+    """The matrices among `params` whose transposed copy the forward GEMMs consume (everything but embedding tables)."""
+    emb_ids = {id(m.weight) for m in model.modules() if isinstance(m, torch.nn.Embedding)} if model is not None else set()
+    return [p for p in params if p.dim() == 2 and id(p) not in emb_ids and min(p.shape) > 1]
+
+
 class _StreamWork:
     """Work handle of a collective that was ENQUEUED on a HIP stream (library-owned communicator): ``wait()`` orders the
     caller's current stream behind it, as the work object of an asynchronous torch.distributed collective does."""
@@ -201,7 +242,13 @@ class FlatTrainer:
 
     def __init__(self, model: torch.nn.Module, lr=1e-4, weight_decay=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  process_group=None, late_prefixes: Sequence[str] = LATE_PREFIXES, check_overlap: bool = False,
-                 always_reduce: bool = False, comm: "LibComm" = None):
+                 always_reduce: bool = False, comm: "LibComm" = None, decoupled_weight_decay: bool = False,
+                 correct_bias: bool = True, no_decay: Sequence[str] = (), max_grad_norm: Optional[float] = None, lr_lambda=None):
+        # decoupled_weight_decay: the BERT rule of optim.AdamW (pytorch_transformers/optimization.py) instead of torch.optim.Adam's:
+        # eps outside the bias correction, which correct_bias=False switches off; weight decay applied to the updated
+        # parameter, 0 for parameters whose name contains one of `no_decay`; max_grad_norm: the reduced gradient, scaled by
+        # 1 / world, is clipped to this global norm inside the update.  lr_lambda(completed steps) scales lr under either rule
+        # (the schedule functions of get_amd.optim fit).  All defaults: the step as it always was.
         self.model = model
         # comm: a library-owned RCCL communicator (LibComm) carries the collectives instead of torch.distributed -- the same
         # calls a C / C++ host of the library would make (gh_flat_allreduce on the caller's stream, stream-ordered)
@@ -225,41 +272,34 @@ class FlatTrainer:
         self._early_snapshot = None
         self.live_names: List[str] = [n for n, _ in live]
         self.params = [p for _, p in live]
-        # every parameter starts on a 256-byte boundary of the flat buffers: the kernels take weights and gradients
-        # straight from these views and need 16-byte aligned rows (a 2-element bias would otherwise shift everything
-        # behind it onto the slow, scalar-load GEMM path); the padding elements stay zero under Adam
-        ALIGN = 64
-        slot = lambda p: (p.numel() + ALIGN - 1) // ALIGN * ALIGN
-        total = sum(slot(p) for p in self.params)
-        self.n_early = sum(slot(p) for n, p in live if not n.startswith(late_prefixes))
-        dev = self.params[0].device
-        self.flat_p = torch.zeros(total, device=dev, dtype=torch.float32)
-        self.flat_g = torch.zeros(total, device=dev, dtype=torch.float32)
-        self.flat_m = torch.zeros(total, device=dev, dtype=torch.float32)
-        self.flat_v = torch.zeros(total, device=dev, dtype=torch.float32)
-        off = 0
-        self._views = []
-        for p in self.params:
-            n = p.numel()
-            self.flat_p[off:off + n].copy_(p.data.reshape(-1))
-            p.data = self.flat_p[off:off + n].view_as(p)
-            gv = self.flat_g[off:off + n].view_as(p)
-            p.grad = gv
-            p._gh_direct_grad = True          # kernels may accumulate straight into this view (ops.weights._direct)
-            self._views.append(gv)
-            off += slot(p)
-        self.numel = total
+        self.n_early = slot_offsets([p.numel() for n, p in live if not n.startswith(late_prefixes)])[1]
+        self.flat_p, self.flat_g, self.flat_m, self.flat_v, self._views, self._offsets = build_flat_bucket(self.params)
+        self.numel = self.flat_p.numel()
         self.t = 0
-        # matrices whose transposed copy the forward GEMMs consume (everything but embedding tables)
-        emb_ids = {id(m.weight) for m in model.modules() if isinstance(m, torch.nn.Embedding)}
-        self._matrices = [p for p in self.params if p.dim() == 2 and id(p) not in emb_ids and min(p.shape) > 1]
+        self._matrices = forward_matrices(model, self.params)
+        # the decoupled rule (optim.AdamW's kernel, gh_adamw_step): per-parameter weight decay, clipping, optional bias correction
+        self.decoupled_weight_decay = bool(decoupled_weight_decay)
+        self.correct_bias, self.max_grad_norm, self.lr_lambda = bool(correct_bias), max_grad_norm, lr_lambda
+        self.no_decay = tuple(no_decay)
+        # every live parameter's weight decay under the decoupled rule, fixed here: 0 where a `no_decay` substring matches its name
+        self._decay = [0.0 if any(s in n for s in self.no_decay) else weight_decay for n in self.live_names]
+        if not self.decoupled_weight_decay and (self.no_decay or max_grad_norm is not None or not self.correct_bias):
+            raise ValueError("get_amd: no_decay, max_grad_norm and correct_bias=False belong to the decoupled rule; pass "
+                             "decoupled_weight_decay=True")
+        if max_grad_norm is not None and not max_grad_norm > 0:
+            raise ValueError(f"get_amd: max_grad_norm={max_grad_norm} must be positive")
+        self.last_grad_norm = None          # 0-dim device tensor of the last clipped step (never read by the trainer itself)
+        self._flat_step = None
 
     # -- checkpoint / resume (the reference saves only net.state_dict(), char_man_fitter_query_repr1.py:143-144;
     #    multi-GPU runs also need the optimiser moments and step count to resume bit-identically)
     def state_dict(self) -> dict:
+        hyper = {"lr": self.lr, "weight_decay": self.weight_decay, "betas": tuple(self.betas), "eps": self.eps}
+        if self.decoupled_weight_decay:      # (the default rule's dict stays as it always was)
+            hyper.update(decoupled_weight_decay=True, correct_bias=self.correct_bias, no_decay=self.no_decay,
+                         max_grad_norm=self.max_grad_norm)
         return {"t": self.t, "m": self.flat_m.detach().cpu().clone(), "v": self.flat_v.detach().cpu().clone(),
-                "names": list(self.live_names), "numel": self.numel,
-                "hyper": {"lr": self.lr, "weight_decay": self.weight_decay, "betas": tuple(self.betas), "eps": self.eps}}
+                "names": list(self.live_names), "numel": self.numel, "hyper": hyper}
 
     def load_state_dict(self, sd: dict):
         assert sd["names"] == self.live_names and sd["numel"] == self.numel, "optimizer state does not match this model"
@@ -399,10 +439,21 @@ class FlatTrainer:
             self._overlap_module = None
 
     def step(self):
-        """all-reduce + fused Adam on the flat bucket (gradient averaged over ranks inside the kernel)."""
+        """all-reduce + fused Adam on the flat bucket (gradient averaged over ranks inside the kernel); under the decoupled
+        rule the norm of the averaged gradient and gh_adamw_step instead."""
         from . import ops
         self.allreduce()
+        lr = self.lr if self.lr_lambda is None else self.lr * self.lr_lambda(self.t)
         self.t += 1
-        ops.adam_step_flat(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.t, lr=self.lr, betas=self.betas,
-                           eps=self.eps, weight_decay=self.weight_decay, grad_scale=1.0 / self.world)
+        if self.decoupled_weight_decay:
+            # all-reduce, norm of the reduced gradient scaled by 1 / world, gh_adamw_step: every parameter at step t
+            if self._flat_step is None:
+                self._flat_step = ops.FlatAdamW(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self._offsets,
+                                                [p.numel() for p in self.params])
+            betas = tuple(self.betas)
+            hypers = [(lr, betas, self.eps, wd, self.correct_bias, self.t) for wd in self._decay]
+            self.last_grad_norm = self._flat_step.step(hypers, grad_scale=1.0 / self.world, max_grad_norm=self.max_grad_norm)
+        else:
+            ops.adam_step_flat(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.t, lr=lr, betas=self.betas,
+                               eps=self.eps, weight_decay=self.weight_decay, grad_scale=1.0 / self.world)
         ops.refresh_transposes(self._matrices)     # k-major copies for the next forward, one launch

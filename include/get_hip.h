@@ -639,6 +639,50 @@ int gh_masked_mean_bwd(const float* g, const int32_t* ids, const float* lens, fl
 int gh_adam_step(float* p, const float* g, float* m, float* v, int64_t count, float lr, float beta1, float beta2,
                  float eps, float weight_decay, int step, float grad_scale, gh_stream_t stream);
 
+/* ---- the BERT fine-tuning optimiser on the same flat bucket (csrc/optim_ops.hip): pytorch_transformers/optimization.py ----
+ * Global gradient norm, replacing the per-parameter norms, their stack and the host read of torch's clip_grad_norm_ that every
+ * BERT recipe runs before optimization.py:130 AdamW.step:
+ *     norm_out[0] = grad_scale * sqrt(sum_{i < count} g[i]^2)            (device memory; the host never reads it)
+ * No floating-point atomics and a fixed order, so two calls on the same gradient give the same bits on any device:
+ *   1. g is cut into chunks of GH_NORM_CHUNK elements, one partial each: gh_flat_grad_norm_partials (host only, no device
+ *      call) says how many doubles `partials` must hold for `count`;
+ *   2. in a chunk, lane t of 256 adds the squares of elements 4 t .. 4 t + 3, then of 1024 + 4 t .., in fp32 (one rounding per
+ *      product and per sum); the 256 lane sums are combined in double: per 64 lanes a butterfly (xor 32, 16, .. 1), then the
+ *      four sums in order;
+ *   3. the partials are summed in double in index order in 256 contiguous runs of ceil(n / 256), the runs' sums in run order;
+ *      root and scale in double, rounded once to fp32.
+ * Two launches (one when count == 0, which writes 0).  g 16-byte aligned; count need not be a multiple of 4. */
+#define GH_NORM_CHUNK 32768
+int gh_flat_grad_norm_partials(int64_t count, int64_t* out_host);
+int gh_flat_grad_norm(const float* g, int64_t count, float grad_scale, double* partials, int64_t n_partials, float* norm_out,
+                      gh_stream_t stream);
+/* AdamW.step, optimization.py:159-187, for the whole bucket in ONE launch, in place on p, m, v (g is only read), with the
+ * hyperparameters of optimization.py:141 `group` per parameter.  The bucket is cut into blocks of GH_ADAMW_BLOCK elements (every
+ * parameter slot of the bucket starts on one); block_seg[count / 64] names each block's entry of seg_table[n_seg], which the
+ * host fills in double and rounds once: step_size = lr, or lr * sqrt(1 - beta2^t) / (1 - beta1^t) with bias correction (:170-174),
+ * lr_wd = lr * weight_decay (:187), one_minus_beta = 1 - beta.  Per element, every operation rounded once to fp32, no FMA:
+ *     gr = (g * grad_scale) * clip
+ *     m  = beta1 * m + one_minus_beta1 * gr                              (:166)
+ *     v  = beta2 * v + (one_minus_beta2 * gr) * gr                       (:167)
+ *     p1 = p - (step_size * m) / (sqrt(v) + eps)                         (:168, :176: eps outside the bias correction)
+ *     p  = p1 - lr_wd * p1   when lr_wd > 0, else p1                     (:186-187)
+ * clip: norm NULL -> 1; else n = norm[0], read on the device (what gh_flat_grad_norm wrote: no host synchronisation):
+ * n <= max_norm -> exactly 1, so that step equals the unclipped one bit for bit; else min(1, max_norm / (n + 1e-6)), the
+ * coefficient of clip_grad_norm_.  The gradient itself is not rescaled in memory.
+ * A block whose entry has skip != 0, or whose id is >= n_seg (checked in the kernel: a bad map cannot read outside the table),
+ * is neither read nor written: padding between slots, and parameters without a gradient this step (:143-144).
+ * Refused before any launch: count not a multiple of 64, p / g / m / v / seg_table not 16-byte aligned, n_seg beyond
+ * GH_ADAMW_MAX_SEGMENTS (what the 16-bit ids can name), a norm with max_norm <= 0. */
+#define GH_ADAMW_BLOCK 64
+#define GH_ADAMW_MAX_SEGMENTS 65535
+typedef struct {
+  float step_size, lr_wd, beta1, beta2, eps, one_minus_beta1, one_minus_beta2;
+  int32_t skip;
+} gh_adamw_seg;
+int gh_adamw_step(float* p, const float* g, float* m, float* v, int64_t count, const uint16_t* block_seg,
+                  const gh_adamw_seg* seg_table, int n_seg, float grad_scale, const float* norm, float max_norm,
+                  gh_stream_t stream);
+
 /* ---- (e) the path's one exchange step: all-reduce(sum) of the flat fp32 gradient bucket over RCCL / xGMI with a
  *      communicator this library owns (SURVEY 8(b) `flat_allreduce`).  The reference has no distributed code -- its
  *      optimiser is single-process (Fitting/FittingFC/declare_fitter.py:58-61) -- so these calls mirror no reference
