@@ -80,6 +80,7 @@ SIGNATURES = {
     "gh_evd_assemble_fwd": [_P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "gh_evd_assemble_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "gh_clamp_events": [_P, _I],
+    "gh_clamp_events_n": [_P, _I, _I],
     "gh_weights_refresh": [_I, _P, _P, _P, _P, _P, _P, _P],
     "gh_seg_offsets": [_P, _I, _P, _P, _I, _P, _P],
     "gh_seg_broadcast": [_P, _P, _P, _I, _I, _P],
@@ -130,6 +131,8 @@ SIGNATURES = {
     "gh_act_fwd": [_P, _P, _I, _I, _I, _P],
     "gh_act_bwd": [_P, _P, _P, _I, _I, _I, _P],
     "gh_bert_embed_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "gh_softmax_xent_fwd": [_P, _L, _I, _P, _I, _L, _L, _I, _P, _P, _P, _P, _P, _P],
+    "gh_softmax_xent_bwd": [_P, _L, _I, _P, _I, _L, _L, _I, _P, _P, _P, _P, _P, _L, _I, _P],
     # library-owned RCCL communicator (csrc/comm_ops.hip; librccl is dlopen'ed on first use)
     "gh_comm_unique_id": [_P],
     "gh_comm_init": [_P, _I, _I, _P],

@@ -71,7 +71,7 @@ inline int few_rows_tag(int groups, int tag) { return groups < PROF_FEW_GROUPS ?
 bool prof_enabled();
 void prof_begin(hipStream_t s, int tag);   // events are recorded only for tags selected by gh_profile_select
 void prof_end(int tag, double work, hipStream_t s);
-unsigned int* clamp_counter();      // four device counters of clamped out-of-range inputs on the current device (gh_clamp_events); NULL = allocation failed
+unsigned int* clamp_counter();      // the GH_CLAMP_SLOTS device counters of clamped out-of-range inputs on the current device (gh_clamp_events_n); NULL = allocation failed
 // Before a launch of `kernel` (the host-side function pointer) with `dynamic_lds` bytes of dynamic shared memory.  At or below the
 // 64 KB every kernel may have it does nothing.  Above, it refuses what the kernel's static LDS plus the request would take beyond
 // the 160 KB of a CU, and lifts the kernel's limit, once per kernel and device, to what is left beside its static LDS.

@@ -50,8 +50,9 @@ void prof_end(int tag, double work, hipStream_t s) {
   g_prof_cur = nullptr;
 }
 
-// Device counters of clamped out-of-range inputs (include/get_hip.h gh_clamp_events): four unsigned ints per device, allocated
-// on first use, handed to the kernels that clamp (cross_entropy: [0], left_assemble: [1], evd_assemble: [2], embed_bwd: [3]).
+// Device counters of clamped out-of-range inputs (include/get_hip.h gh_clamp_events, gh_clamp_events_n): GH_CLAMP_SLOTS unsigned
+// ints per device, allocated on first use, handed to the kernels that clamp (cross_entropy: [0], left_assemble: [1],
+// evd_assemble: [2], embed_bwd: [3], softmax_xent_fwd: [4]).
 static std::mutex g_clamp_mu;
 static std::unordered_map<int, unsigned int*> g_clamp_buf;
 unsigned int* clamp_counter() {
@@ -61,8 +62,8 @@ unsigned int* clamp_counter() {
   auto it = g_clamp_buf.find(dev);
   if (it != g_clamp_buf.end()) return it->second;
   unsigned int* p = nullptr;
-  if (hipMalloc((void**)&p, 4 * sizeof(unsigned int)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  if (hipMemset(p, 0, 4 * sizeof(unsigned int)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(p); return nullptr; }
+  if (hipMalloc((void**)&p, GH_CLAMP_SLOTS * sizeof(unsigned int)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+  if (hipMemset(p, 0, GH_CLAMP_SLOTS * sizeof(unsigned int)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(p); return nullptr; }
   g_clamp_buf.emplace(dev, p);
   return p;
 }
@@ -107,17 +108,19 @@ int lds_opt_in(const void* kernel, size_t dynamic_lds, const char* who) {
 
 using namespace gh;
 
-extern "C" int gh_clamp_events(int64_t* out, int reset) {
+extern "C" int gh_clamp_events_n(int64_t* out, int n, int reset) {
   GH_REQUIRE(out, "clamp_events: NULL output");
+  GH_REQUIRE(n >= 1 && n <= GH_CLAMP_SLOTS, "clamp_events: %d slots asked for (1 .. %d)", n, GH_CLAMP_SLOTS);
   unsigned int* p = clamp_counter();
   GH_REQUIRE(p, "clamp_events: cannot allocate the counter");
-  unsigned int h[4] = {0, 0, 0, 0};
+  unsigned int h[GH_CLAMP_SLOTS] = {};
   GH_CHECK_HIP(hipDeviceSynchronize());
   GH_CHECK_HIP(hipMemcpy(h, p, sizeof(h), hipMemcpyDeviceToHost));
-  for (int i = 0; i < 4; ++i) out[i] = (int64_t)h[i];
+  for (int i = 0; i < n; ++i) out[i] = (int64_t)h[i];
   if (reset) GH_CHECK_HIP(hipMemset(p, 0, sizeof(h)));
   return 0;
 }
+extern "C" int gh_clamp_events(int64_t* out, int reset) { return gh_clamp_events_n(out, 4, reset); }
 
 extern "C" int gh_abi_version(void) { return GH_ABI_VERSION; }
 extern "C" const char* gh_last_error(void) { return g_err; }

@@ -1327,3 +1327,6 @@ class RankCrossEntropyLoss(nn.Module):
 
 # ------------------------------------------------------------------ matchzoo/modules/bert_module.py:9-30 (get_amd/bert.py)
 from .bert import BertConfig, BertModel, BertModule  # noqa: E402,F401
+from .bert import (BertForMaskedLM, BertForMultipleChoice, BertForNextSentencePrediction, BertForPreTraining,  # noqa: E402,F401
+                   BertForQuestionAnswering, BertForSequenceClassification, BertForTokenClassification, BertLMPredictionHead,
+                   BertOnlyMLMHead, BertOnlyNSPHead, BertPredictionHeadTransform, BertPreTrainingHeads)

@@ -628,6 +628,10 @@ int gh_evd_assemble_bwd(const float* g, const int32_t* offsets, const void* sour
  * the last reset.  Synchronises the device.  A training loop checks it once per epoch (or per step in debug runs): a non-zero
  * count means corrupt input data was trained on as if it were class / row 0 or the last one. */
 int gh_clamp_events(int64_t* out4_host, int reset);
+/* The same counters with the slots added since: out_host[0 .. n), 1 <= n <= GH_CLAMP_SLOTS.  [4] = labels outside [0, c) other than
+ * the ignore index seen by gh_softmax_xent_fwd (the row is dropped from the loss).  Either call's reset clears every slot. */
+#define GH_CLAMP_SLOTS 5
+int gh_clamp_events_n(int64_t* out_host, int n, int reset);
 /* masked mean over claim nodes (graph_based_semantic_structure.py:153): dst[b][h] = sum_l hid*mask / len */
 int gh_masked_mean_fwd(const float* hid, const int32_t* ids, const float* lens, float* dst, int b, int l, int h,
                        gh_stream_t stream);
@@ -1022,6 +1026,37 @@ int gh_act_bwd(const float* x, const float* g, float* dx, int rows, int n, int m
 int gh_bert_embed_fwd(const float* word, const float* pos, const float* type, const int32_t* ids, const int32_t* pos_ids,
                       const int32_t* type_ids, const float* gamma, const float* beta, float eps, int rows, int l, int d,
                       int vocab, int npos, int ntype, float* sum, float* y, float* mean, float* rstd, gh_stream_t stream);
+
+/* ---- softmax cross-entropy with an ignore index (csrc/loss_ops.hip): the CrossEntropyLoss(ignore_index) every task model of
+ *      pytorch_transformers/modeling_bert.py ends in (:698, :765, :822, :890, :996, :1056, :1142), up to the masked-LM loss over
+ *      (B * L, vocab_size) logits ----
+ * Logits: fp32, element (r, j) at x[r * ldx + j * cs], cs >= 1, ldx >= (c - 1) * cs + 1: a column slice of a wider tensor, or
+ * one of the two columns of the question-answering head's (B, L, 2) output (cs = 2, ldx = 2 L), is read in place.  labels[rows]:
+ * int64 (labels_i64 != 0) or int32.  A row is KEPT iff its label is not ignore_index and lies in [0, c); ignore_index is any
+ * 64-bit value (-1, -100, c).  A label outside [0, c) that is not ignore_index makes torch raise; here the row is dropped like
+ * an ignored one and counted in slot [4] of gh_clamp_events_n, and nothing is read or written through it.
+ * Forward: lse[r] = log sum_j exp(x[r][j]) for EVERY row, by a running maximum m and sum s (one read of the logits, no exp
+ * overflow), rounded to fp32, and lse_lo[r] = (m + log s) - lse[r], what that rounding dropped: at logits of 1e4 fp32 has a grid
+ * of 2^-10, and probabilities formed from lse[r] alone would be off by a relative 5e-4.  row_loss[r] (scratch of `rows`
+ * floats) = (m - x[r][label]) + log s for a kept row, 0 otherwise; then
+ *     n_kept[0] = the number of kept rows,   loss[0] = (sum over kept rows of row_loss) / n_kept      (NaN when no row is kept)
+ * summed without floating-point atomics in a fixed order: in double, in 256 contiguous runs of ceil(rows / 256) rows in row
+ * order, the runs' sums in run order, rounded once to fp32.  Two calls give the same bits, and so do a strided view and its
+ * contiguous copy (the float4, float2 and element-wise variants of a path share the order of every operation).  c = 1: loss 0.
+ * Backward: dx[r * lddx + j * dcs] = (exp((x[r][j] - lse[r]) - lse_lo[r]) - [j == label_r]) * g[0] / n_kept[0] for a kept row and exactly 0
+ * for every other row; g (the upstream gradient of the scalar loss) and n_kept are read on the device.  One read of the
+ * logits, one write of dx, one writer per element; what lies between the rows or the elements of dx is not touched.  Only lse
+ * and lse_lo, two floats per row, live between the two calls.
+ * Paths by c: <= 32 one lane per row, <= 2048 one wave per row, wider one workgroup per row; the two wide paths with float4
+ * accesses where cs (and dcs) == 1 and base and row stride are multiples of 16 bytes, float2 where they are multiples of 8 (a
+ * contiguous matrix of 30522-wide rows: 30522 = 2 mod 4), element-wise otherwise; the three give the same bits.
+ * Refused: NULL pointers, rows <= 0 (an empty input is the caller's to answer) or > 2^31 - 1, c <= 0, cs or dcs < 1, a row
+ * stride below the span of a row. */
+int gh_softmax_xent_fwd(const float* x, int64_t ldx, int cs, const void* labels, int labels_i64, int64_t ignore_index, int64_t rows,
+                        int c, float* lse, float* lse_lo, float* row_loss, float* loss, int64_t* n_kept, gh_stream_t stream);
+int gh_softmax_xent_bwd(const float* x, int64_t ldx, int cs, const void* labels, int labels_i64, int64_t ignore_index, int64_t rows,
+                        int c, const float* lse, const float* lse_lo, const float* g, const int64_t* n_kept, float* dx, int64_t lddx,
+                        int dcs, gh_stream_t stream);
 
 /* Everything the forward / backward need that is DERIVED from weight matrices, for n matrices in one launch (after the
  * optimiser step): dst_t[i] = src[i]^T as fp32 [cols][rows] (the backward's dX operands), and -- bf16 storage mode, any of the
